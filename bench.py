@@ -31,13 +31,20 @@ them (and, for N > 1, after the all_gather and a barrier across ranks).
 Inputs are resident in HBM before the timed region. Each rank fits its own series (seed =
 rank * fits + f): weak scaling.
 
-After the timed region (rank 0, one GPU only; never part of `value`): the CPU baseline, and two
-secondary lines the driver times with the rest of the run — config C4 on the dense path
-(Matern52, D = 5, N = 4096: fits/s and the fused K⁻¹ + gradient contraction's roofline) and
-config C5 (SVGP, N = 65536, M = 1024: ms per ELBO + gradient evaluation).
+A plain run sets up, warms up, times the K steps and prints the result line. With `--full`, after
+the timed region (rank 0, one GPU only; never part of `value`): the CPU baseline, and the
+secondary lines timed with the rest of the run — the reference's one-at-a-time pattern (C1 sizes
+and C2), the C3 batch, config C4 on the dense path (Matern52, D = 5, N = 4096: fits/s and the
+fused K⁻¹ + gradient contraction's roofline) and config C5 (SVGP, N = 65536, M = 1024: ms per
+ELBO + gradient evaluation).
 
-Launch: python bench.py [--gpus 1 --steps K --warmup W]; for N>1 the driver uses
-python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
+`--dump-outputs DIR` writes what the last timed step computed (every fit's summary row and the
+whole predict_f of a fixed sample of its fits) as float64 .npy files, after the clock has
+stopped; the series are seeded and a fit's bits do not depend on what shares its device call, so
+two runs with the same arguments write the same arrays.
+
+Launch: python bench.py [--gpus 1 --steps K --warmup W] [--full] [--dump-outputs DIR]; for N>1
+the driver uses python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
 """
 from __future__ import annotations
 
@@ -58,6 +65,8 @@ NOISE = 1e-5
 MAXITER = 100
 FP64_PEAK_TFLOPS = 78.6  # MI355X dense FP64 (matrix) datasheet peak, /opt/skills/guides/MI355X_MICROARCH.md
 WAVE_SLOTS = 2048        # band16 sweep places: 256 CUs x 4 SIMDs x 2 waves (one wavefront per problem)
+DUMP_SAMPLE = 8          # --dump-outputs: fits per host process whose whole predict_f is written
+DUMP_SEED = 20240       # seed of that sample (+ the process index)
 
 
 def synthetic_series(n: int, seed: int, lengthscale: float = 64.0, n_features: int = 2048,
@@ -69,10 +78,31 @@ def synthetic_series(n: int, seed: int, lengthscale: float = 64.0, n_features: i
     w = rng.standard_normal(n_features) / lengthscale
     b = rng.uniform(0.0, 2.0 * math.pi, n_features)
     coef = rng.standard_normal(n_features)
-    f = np.sqrt(2.0 / n_features) * (np.cos(np.outer(x, w) + b) @ coef)
+    ph = np.outer(x, w)  # (the same elementwise operations in one [n, n_features] buffer)
+    ph += b
+    np.cos(ph, out=ph)
+    f = np.sqrt(2.0 / n_features) * (ph @ coef)
     y = f + noise_std * rng.standard_normal(n)
     y = (y - y.mean()) / y.std(ddof=1)
     return x.reshape(-1, 1), y.reshape(-1, 1)
+
+
+def series_batch(n, seeds, procs):
+    """synthetic_series of every seed, in order. Setup only: most of a series' time is numpy's cos
+    over its feature matrix, which releases the GIL, so a few host threads (the job's CPUs over
+    the GPU's host processes, which all generate at once) make them side by side; each series is
+    computed exactly as by a lone call. BLAS stays on the calling thread meanwhile: a series' one
+    matrix-vector product is a thousandth of its time, and a BLAS pool per host process, spinning
+    after each product, takes the job's CPUs from the cos."""
+    import threadpoolctl
+    ranks = max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1")))
+    threads = max(1, min(4, job_cpus()[0] // (max(procs, 1) * ranks), len(seeds)))
+    with threadpoolctl.threadpool_limits(limits=1, user_api="blas"):
+        if threads == 1:
+            return [synthetic_series(n, s) for s in seeds]
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(threads) as ex:
+            return list(ex.map(lambda s: synthetic_series(n, s), seeds))
 
 
 def job_cpus():
@@ -362,8 +392,19 @@ def parse_args(argv=None):
                     help="strong scaling: fits per step over all ranks")
     ap.add_argument("--total-series", type=int, default=int(os.environ.get("GPX_BENCH_TOTAL_SERIES", 8 * 512)),
                     help="strong scaling: distinct series of the batch (fit i fits series i mod this)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the C4 / C5 secondary lines")
+    # a plain run does only what the headline figure needs; the CPU baseline and the secondary
+    # lines (runs of their own, minutes together) are behind --full
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also time the CPU baseline and the secondary lines (C1, solo, C3, "
+                         "C4, C5); one GPU only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the C1 .. C5 secondary lines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy "
+                         "(float64): fit_summary [fits, 6] = every fit's lengthscale*, variance*, loss*, nfev and the "
+                         "mean / variance of its last training-point prediction; predict_mean / predict_var "
+                         "[sample, N] = predict_f at the training inputs of a fixed sample of the step's fits, "
+                         "predict_fit_index [sample] = their rows in fit_summary")
     return ap.parse_args(argv)
 
 
@@ -429,7 +470,7 @@ class FitWorker:
             self.F, self.S = len(self.fit_ids), len(seeds)
             pos = {sd: k for k, sd in enumerate(seeds)}
             self.series_of = [pos[i % args.total_series] for i in self.fit_ids]
-            data = [synthetic_series(n, sd) for sd in seeds]
+            data = series_batch(n, seeds, P)
         else:
             F = args.fits
             self.F = share(F, P, w)
@@ -439,7 +480,7 @@ class FitWorker:
             self.S = share(S, P, w)
             s0 = sum(share(S, P, i) for i in range(w))
             self.series_of = [f % self.S for f in range(self.F)]
-            data = [synthetic_series(n, rank * S + s0 + s) for s in range(self.S)]
+            data = series_batch(n, [rank * S + s0 + s for s in range(self.S)], P)
         self.Xd = [torch.as_tensor(x, device=dev) for x, _ in data]  # resident in HBM before timing
         self.Yd = [torch.as_tensor(y, device=dev) for _, y in data]
         # read-only series: their band-table boxes are computed at the first rebind and reused
@@ -475,6 +516,7 @@ class FitWorker:
         self.opt = gpx.optimizers.Scipy()
         self.width, self.groups = W, G
         self.traces, self.driver_stats = [], []
+        self.kept = None
 
     def make_model(self, f):
         # GPflow defaults (σ²=1, ℓ=1), σn² = 1e-5 frozen — GPR/model_trainer.py:15-17
@@ -486,10 +528,11 @@ class FitWorker:
         gpx.set_trainable(m.likelihood.variance, False)
         return m
 
-    def run_steps(self, k):
+    def run_steps(self, k, keep=False):
         """k steps (k × F_w fits, each from GPflow defaults) streamed back to back through the
         slots; returns (nfev list, summary rows [k·F_w, 6] on the host: ℓ*, σ²*, loss*, nfev,
-        mean and var of the last training-point prediction)."""
+        mean and var of the last training-point prediction). `keep`: hold on to the last step's
+        predictions for last_step_outputs (--dump-outputs; read after the clock has stopped)."""
         torch, F = self.torch, self.F
         # every fit's model is built inside the timed region, on demand (as the reference's loop
         # builds each GPR right before fitting it), while the host thread waits for the device
@@ -511,7 +554,22 @@ class FitWorker:
             ids = np.asarray(self.fit_ids, dtype=np.float64)
             gidx = np.concatenate([ids + st * self.args.total_fits for st in range(k)])
             table = np.concatenate([gidx[:, None], table], axis=1)
+        if keep and k > 0:
+            self.kept = (table[(k - 1) * F:], preds[(k - 1) * F:])
         return [r.nfev for r in res], table
+
+    def last_step_outputs(self, sample=DUMP_SAMPLE):
+        """What run_steps(k, keep=True) computed in its last step, on the host in float64: this
+        process's summary rows [F_w, cols], and predict_f (mean [s, n], var [s, n]) of a fixed
+        sample of s = min(sample, F_w) of its fits with their positions in the rows (the whole
+        step's predictions are 2 x 8 x n bytes per fit: 400 MB at the defaults). The sample is
+        seeded by the process index, so it is the same from run to run."""
+        rows, preds = self.kept
+        pick = np.sort(np.random.default_rng(DUMP_SEED + self.w).choice(len(preds), size=min(sample, len(preds)),
+                                                                        replace=False))
+        mean = np.stack([preds[i][0].reshape(-1).cpu().numpy() for i in pick]) if len(pick) else np.empty((0, self.n))
+        var = np.stack([preds[i][1].reshape(-1).cpu().numpy() for i in pick]) if len(pick) else np.empty((0, self.n))
+        return rows, pick, mean.astype(np.float64), var.astype(np.float64)
 
     def reset_timing(self):
         for e in self.engines:
@@ -532,10 +590,11 @@ class FitWorker:
         return out
 
 
-def helper_main(w, P, argv, rank, gpu, start, q, admission=None):
+def helper_main(w, P, argv, rank, gpu, start, q, admission=None, dq=None):
     """A helper host process (spawned before the rank touched the GPU): warm up, report ready,
     wait for the rank's start signal, fit its slice of the K steps, synchronise, hand back its
-    results (the message means its device work is done)."""
+    results (the message means its device work is done); with --dump-outputs, then its last
+    step's outputs through `dq`."""
     os.environ["GPX_DEVICE"] = str(gpu)
     args = parse_args(argv)
     import torch
@@ -548,11 +607,13 @@ def helper_main(w, P, argv, rank, gpu, start, q, admission=None):
     q.put(("ready", w))
     start.wait()
     t0 = time.perf_counter()
-    nfev, summary = wk.run_steps(args.steps)
+    nfev, summary = wk.run_steps(args.steps, keep=dq is not None)
     torch.cuda.synchronize()
     busy = time.perf_counter() - t0
     q.put(("done", (w, nfev, summary, wk.timing(), wk.driver_stats[-1] if wk.driver_stats else None, busy,
                     wk.wave_records())))
+    if dq is not None:
+        dq.put(("dump", (w,) + wk.last_step_outputs()))
     if os.environ.get("GPX_SUBMIT_STATS"):
         wk.engines.clear()  # destroyed now: the library prints the per-batch submit phases
 
@@ -575,6 +636,21 @@ def collect(q, helpers, kind, timeout):
         assert k == kind, (k, kind)
         got.append(v)
     return got
+
+
+def write_outputs(path, dumps):
+    """--dump-outputs: the host processes' last_step_outputs, in process order, as float64 .npy
+    files under `path` (a fit's row in fit_summary is its place in the step: process by process,
+    each in the order of its slice)."""
+    os.makedirs(path, exist_ok=True)
+    dumps = sorted(dumps, key=lambda d: d[0])
+    base = np.cumsum([0] + [len(d[1]) for d in dumps])
+    arrays = {"fit_summary": np.concatenate([d[1] for d in dumps]),
+              "predict_fit_index": np.concatenate([d[2] + b for d, b in zip(dumps, base)]),
+              "predict_mean": np.concatenate([d[3] for d in dumps]),
+              "predict_var": np.concatenate([d[4] for d in dumps])}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def wave_trace_summary(recs, wall_s, clock_hz=1e8):
@@ -1005,16 +1081,18 @@ def main():
 
     # helper processes first, before anything here touches the GPU (a process that has
     # initialised HIP must not fork/exec)
-    helpers, start, q, admission = [], None, None, None
+    helpers, start, q, admission, dq = [], None, None, None, None
+    dump = args.dump_outputs if rank == 0 else None  # (rank 0's part of the step: the whole of it on one GPU)
     if P > 1:
         import multiprocessing as mp
         ctx = mp.get_context("spawn")
         start = ctx.Event()
         q = ctx.Queue()
+        dq = ctx.Queue() if dump else None
         # (optimizers.DeviceAdmission's semaphore, made here without importing the package: nothing
         # may touch the GPU before the helpers are spawned)
         admission = ctx.BoundedSemaphore(args.admission) if args.admission > 0 else None
-        helpers = [ctx.Process(target=helper_main, args=(w, P, argv, rank, gpu, start, q, admission), daemon=True)
+        helpers = [ctx.Process(target=helper_main, args=(w, P, argv, rank, gpu, start, q, admission, dq), daemon=True)
                    for w in range(1, P)]
         for h in helpers:
             h.start()
@@ -1049,7 +1127,7 @@ def main():
     torch.cuda._sleep(1000)
     if start is not None:
         start.set()                     # the helpers start their steps
-    nfev, summary = wk.run_steps(args.steps)
+    nfev, summary = wk.run_steps(args.steps, keep=bool(dump))
     torch.cuda._sleep(1000)
     torch.cuda.synchronize()
     busy0 = time.perf_counter() - t0
@@ -1072,6 +1150,9 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if dump:
+        dumps = [(0,) + wk.last_step_outputs()] + (collect(dq, helpers, "dump", 600) if helpers else [])
+        write_outputs(dump, dumps)
     for h in helpers:
         h.join(timeout=120)
     if os.environ.get("GPX_SUBMIT_STATS"):
@@ -1281,9 +1362,9 @@ def main():
         out["wave_trace"] = wave_trace_summary([p[6] for p in parts], elapsed)
         if os.environ.get("GPX_WAVE_TRACE_OUT"):  # raw records per host process (tools/wave_overlap.py)
             np.savez_compressed(os.environ["GPX_WAVE_TRACE_OUT"], **{f"proc{p[0]}": p[6] for p in parts})
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(n, nfev_mean)
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary:
         for name, fn in (("secondary_c1_solo", lambda: secondary_c1_solo(gpu)),
                          ("secondary_solo", lambda: secondary_solo(gpu)),
                          ("secondary_c3_batch", lambda: secondary_c3(gpu)),

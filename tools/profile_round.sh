@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round evidence on the GPU box (run from the repo root via gpurun):
-#   0. the bench line itself (python bench.py: the defaults, CPU baseline and secondary lines included)
+#   0. the bench line itself (python bench.py --full: the defaults, CPU baseline and secondary lines included)
 #   1. rocprofv3 --kernel-trace --stats of a shorter bench (20 steps) -> per-kernel summary + trace check
 #   2. --pmc FETCH_SIZE, 3. --pmc WRITE_SIZE (separate passes) -> HBM bytes of the roofline kernel
 #   4. --pmc MFMA busy / fp64 MOPS / GUI_ACTIVE               -> MFMA utilisation per kernel
@@ -11,7 +11,7 @@ TAG=${1:-r02}
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
-timeout -k 10 600 python3 "$ROOT/bench.py" > "$OUT/bench.log" 2>&1
+timeout -k 10 600 python3 "$ROOT/bench.py" --full > "$OUT/bench.log" 2>&1
 cd /tmp && export TMPDIR=/tmp
 # counter passes serialise every dispatch: one host process and a short run (bytes and MFMA
 # counts per problem do not depend on the process count)

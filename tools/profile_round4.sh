@@ -13,7 +13,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 if [ -z "$SKIP_BENCH" ]; then  # (SKIP_BENCH=1: the caller has just run the default bench line)
-  timeout -k 10 600 python3 "$ROOT/bench.py" > "$OUT/bench.log" 2>&1
+  timeout -k 10 600 python3 "$ROOT/bench.py" --full > "$OUT/bench.log" 2>&1
   tail -1 "$OUT/bench.log" | cut -c1-300
 fi
 GPX_WAVE_TRACE=1 GPX_WAVE_TRACE_OUT="$OUT/wave_trace.npz" timeout -k 10 300 python3 "$ROOT/bench.py" \

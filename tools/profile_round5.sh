@@ -15,7 +15,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 if [ -z "$SKIP_BENCH" ]; then
-  timeout -k 10 600 python3 "$ROOT/bench.py" > "$OUT/bench.log" 2>&1
+  timeout -k 10 600 python3 "$ROOT/bench.py" --full > "$OUT/bench.log" 2>&1
   tail -1 "$OUT/bench.log" | cut -c1-200
 fi
 cd /tmp && export TMPDIR=/tmp
