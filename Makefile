@@ -24,7 +24,12 @@ $(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/gpx_internal.h $(CSRC)/gpx_host.h $(CSRC)/gpx
 $(CSRC)/gpx_host_math.o: $(CSRC)/gpx_host_math.c include/gpx.h
 	gcc -O2 -fno-builtin -fno-fast-math -fPIC -std=c11 -Wall -c $< -o $@
 
-$(LIB): $(CSRC)/gpx_kernels.o $(CSRC)/gpx_api.o $(CSRC)/gpx_band.o $(CSRC)/gpx_band16.o $(CSRC)/gpx_bcr.o $(CSRC)/gpx_svgp_kernels.o $(CSRC)/gpx_svgp.o $(CSRC)/gpx_host_math.o
+# the library's objects (the phases library below swaps in its three instrumented ones)
+OBJS := $(addprefix $(CSRC)/,gpx_kernels.o gpx_api.o gpx_knobs.o gpx_dense.o gpx_route.o gpx_eval.o gpx_predict.o \
+  gpx_band.o gpx_band16.o gpx_bcr.o gpx_svgp_kernels.o gpx_svgp.o gpx_host_math.o)
+$(OBJS): $(CSRC)/gpx_knobs.h
+
+$(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,-soname,libgpx.so $^ -o $@
 
 # plain-C consumer of the C ABI (gcc, HIP runtime API only), run by tests/test_c_abi_gpu.py
@@ -42,7 +47,8 @@ $(CSRC)/gpx_band16_phases.o: $(CSRC)/gpx_band16.hip $(CSRC)/gpx_internal.h $(CSR
 	$(HIPCC) $(HIPFLAGS) -DGPX_BAND_PHASES -c $< -o $@
 $(CSRC)/gpx_bcr_phases.o: $(CSRC)/gpx_bcr.hip $(CSRC)/gpx_internal.h $(CSRC)/gpx_b16core.h $(CSRC)/gpx_kfun.h
 	$(HIPCC) $(HIPFLAGS) -DGPX_BCR_PHASES -c $< -o $@
-$(PHASES_LIB): $(CSRC)/gpx_kernels.o $(CSRC)/gpx_api.o $(CSRC)/gpx_band_phases.o $(CSRC)/gpx_band16_phases.o $(CSRC)/gpx_bcr_phases.o $(CSRC)/gpx_svgp_kernels.o $(CSRC)/gpx_svgp.o $(CSRC)/gpx_host_math.o
+PHASED := gpx_band gpx_band16 gpx_bcr
+$(PHASES_LIB): $(foreach o,$(OBJS),$(if $(filter $(PHASED),$(basename $(notdir $(o)))),$(o:.o=_phases.o),$(o)))
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,-soname,libgpx_phases.so $^ -o $@
 phases: $(PHASES_LIB)
 
@@ -56,6 +62,7 @@ clean:
 HARNESS := tests/c/host_harness
 HSRC := $(wildcard $(CSRC)/*.hip)
 HOBJ := $(patsubst $(CSRC)/%.hip,build/asan/%.o,$(HSRC))
+$(HOBJ) build/asan/host_harness.o: $(CSRC)/gpx_knobs.h
 HSAN := -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-sanitize-recover=undefined \
   -Xarch_host -fno-omit-frame-pointer -g -O1
 build/asan/%.o: $(CSRC)/%.hip $(CSRC)/gpx_internal.h $(CSRC)/gpx_host.h $(CSRC)/gpx_kfun.h $(CSRC)/gpx_leaf.h $(CSRC)/gpx_b16core.h include/gpx.h

@@ -1123,10 +1123,7 @@ static void launch16_q(const BandFusedArgs& a, int max_terms, bool se1, int kin,
                        hipEvent_t* ev) {
   kin = se1 ? kin : 0;
   // GPX_B16_FUSED=1: the SE1 classes' sweeps as one fused launch (fwd then bwd per wavefront)
-  static const bool fused = [] {
-    const char* e = getenv("GPX_B16_FUSED");
-    return e && atoi(e) != 0;
-  }();
+  static const bool fused = knob_on(Knob::B16Fused);
   if (se1 && fused) {
     auto fk = (kin & 1) ? ((kin & 2) ? band16_fused_kernel<Q, true, true> : band16_fused_kernel<Q, true, false>)
                         : ((kin & 2) ? band16_fused_kernel<Q, false, true> : band16_fused_kernel<Q, false, false>);

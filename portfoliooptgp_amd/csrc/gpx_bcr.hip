@@ -1368,10 +1368,7 @@ void bcr_graph_cache_free(void* cache) {
 }
 
 void launch_bcr(const BcrArgs& a, int Q, int max_terms, int np, int Nmax, hipStream_t s, void** cache) {
-  static const bool graphs = [] {
-    const char* e = getenv("GPX_BCR_GRAPH");
-    return !(e && atoi(e) == 0);
-  }();
+  static const bool graphs = knob_on(Knob::BcrGraph);
   if (!graphs || !cache) return launch_bcr_direct(a, Q, max_terms, np, Nmax, s);
   if (!*cache) *cache = new BcrGraphCache();
   BcrGraphCache& gc = *static_cast<BcrGraphCache*>(*cache);

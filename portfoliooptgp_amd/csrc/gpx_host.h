@@ -1,8 +1,10 @@
-// gpx_host.h — host-side internals shared by the exact-GP (gpx_api.hip) and SVGP
-// (gpx_svgp.hip) orchestration: context / batch state, error plumbing and the device
-// building blocks (K build + recursive Cholesky-and-inverse, batched MFMA GEMM).
+// gpx_host.h — host-side internals shared by the exact-GP host files (gpx_api.hip: lifetime,
+// rebinds, setters; gpx_dense.hip; gpx_route.hip; gpx_eval.hip; gpx_predict.hip) and the SVGP
+// orchestration (gpx_svgp.hip): context / batch state, error plumbing and the device building
+// blocks (K build + recursive Cholesky-and-inverse, batched MFMA GEMM).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <chrono>
 #include <memory>
 #include <string>
 #include <vector>
@@ -100,7 +102,7 @@ struct gpx_batch {
   // (gpx_batch_rebind_device_boxed) and the gather needs no box download + synchronise
   std::vector<double> slot_box;
   std::vector<char> slot_box_ok;
-  // the evaluation submitted by gpx_batch_lml_grad_submit, completed by _complete (gpx_api.hip)
+  // the evaluation submitted by gpx_batch_lml_grad_submit, completed by _complete (gpx_eval.hip)
   struct PendingEval;
   std::unique_ptr<PendingEval> pending_eval;
   std::vector<PendingRebind> pend;
@@ -300,29 +302,88 @@ void route_call(gpx_batch* bt, int n_active, const int32_t* active, const double
 // the per-call limits of the routing, and one problem's path under them (w: its band width, in
 // 16-blocks for kRouteBand16, in 64-blocks otherwise, -1 when not banded)
 struct RouteLimits { int plim = -1, q16lim = -1, q16wide = -1; bool fused_on = true; };
-int b16_inline_k();                            // GPX_B16_INLINE_K (bit 0 forward, bit 1 backward)
-int b16_inline_k_wide();                       // ... for the wide launch (GPX_B16_INLINE_K_WIDE)
-int wide_bcr_mode();                            // GPX_WIDE_BCR: 0 never, 1 on the reduction route (default), 2 always
-bool wide_bcr_on(bool bcr_route);               // band16 widths Q > kBcrMaxQ by the bs = 128 reduction in this call
-long long bcr_ws_need(const int* q, const int* cnt, int g0, int g1, int Nmax);  // workspace of groups g0..g1-1
-int wide_qmax(bool se1);                       // widest class of the wide launch (5, or 8: GPX_WIDE_QMAX)
+// (the knobs and the rules derived from them, b16_inline_k .. bcr_max_problems: gpx_knobs.h)
 bool se1_spec(const gpx_kernel_spec& sp);     // one SquaredExponential term on one column
 enum RouteKind { kRouteDense, kRouteShadow, kRouteBand, kRouteFused, kRouteBand16 };
 RouteLimits route_limits(const gpx_batch* bt);
 RouteKind route_one(const gpx_batch* bt, int b, const double* theta_row, const RouteLimits& L, int& w);
+
+// ---- the lanes of a fused range (gpx_eval.hip) ----
+// The width classes of a call are independent: each class's chain (its K band build, then its
+// sweeps or its reduction) is a lane, and the lanes run concurrently. What a lane runs:
+enum class LaneKind {
+  Band16,   // the band16 sweeps of one width group
+  Fused1,   // the 64-row sweeps' p <= 1 class
+  Fused2,   // the 64-row sweeps' p = 2 class
+  Wide16,   // the wide SE1 launch (band16_wide_kernel) over adjacent width groups
+  Bcr,      // the block-cyclic-reduction chain of one width group (Q <= kBcrMaxQ)
+  BcrWide,  // the block-128 reduction chain of the widths kBcrMaxQ + 1 .. kBand16MaxQ
+};
+// problems [off, off + n) of the range; band16 groups [g, g_end) (0, 0 for the 64-row classes);
+// wso: a reduction lane's offset into the reduction workspace, in doubles
+struct Lane { LaneKind kind; int g, g_end, n, off; long long wso; };
+constexpr int kMaxLanes = kBand16MaxQ + 2;
+struct LanePlan {
+  Lane lanes[kMaxLanes];
+  int nl = 0;
+  long long ws_need = 0;   // doubles of reduction workspace the lanes use (0: none)
+  int bcr_wide_evals = 0;  // problems on BcrWide lanes (the profiling counter of that name)
+};
+// the knob-derived limits a plan depends on
+struct LaneLimits {
+  int wide_qmax;   // wide_qmax(se1)
+  bool wide_bcr;   // wide_bcr_on(bcr_q > 0)
+  int lane_order;  // GPX_LANE_ORDER
+};
+// The lanes of a range [band16 groups (n_g16 of widths g16_q, sizes g16_n: n16 problems) | p <= 1
+// (n1) | p = 2 (the rest of na)], largest first (lane_order 1: the largest last). Pure host logic.
+LanePlan plan_lanes(int n_g16, const int* g16_q, const int* g16_n, int n16, int n1, int na, bool se1, int bcr_q,
+                    int wide_from, const LaneLimits& lim, int Nmax);
+// what a call's fused range runs now and what goes out as a deferred slow part
+struct DeferSplit { int n_slow, n_g16_run, n16_run, n_fused1_run; };
+// head: the call's problems ahead of the fused range (dense and per-block band). Pure.
+DeferSplit split_deferred(int defer_q, int bcr_q, int head, int n_g16, const int* g16_q, const int* g16_n, int n16,
+                          int n_fused1, int n_fused);
 // p <= 2: [band16 groups (sizes g16_n, widths g16_q; K band of kband16 64-block diagonals) |
 // p<=1 (n1) | p=2]
 int band_fused_eval(const Run& r, int n16, int n_g16, const int* g16_q, const int* g16_n, bool se1, int kband16,
                      int n1, int max_terms, hipEvent_t* ev = nullptr, hipEvent_t (*ev16)[4] = nullptr);
-double band_fused_flops(int Np, int p, bool fwd);  // block-product flops of one problem's sweep
+double band_fused_flops(int Np, int p, bool fwd);  // block-product flops of one problem's sweep (gpx_api.hip)
+double band16_flops(int Np, int Q, bool fwd);      // MFMA flops of one problem's band16 sweep (gpx_api.hip)
 void factor(const Run& r);       // K build + recursive Cholesky-and-inverse (W = L⁻¹)
 void alpha_solve(const Run& r);  // z = W y, α = Wᵀ z
+void contract(const Run& r, int max_terms, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);  // WᵀW ∘ ∂K/∂θ
+void reduce(const Run& r);       // the contraction's partials -> results
+bool small64_on(const gpx_batch* bt);  // this batch's dense evaluations are one fused launch (Np = 64, 128)
+void small64_eval(const Run& r, bool grad, char* sio = nullptr, int tag = 0);
 int upload_common(gpx_batch* bt, int n_active, const int32_t* active, const double* theta,
                   hipStream_t s, bool predict_block = false);
 int flush_rebinds(gpx_batch* bt, hipStream_t s);  // pending rebinds -> device (one gather on s)
 int wait_io(gpx_batch* bt);                        // the last asynchronous call's uploads have left h_io
 int fence_io(gpx_batch* bt, hipStream_t s);        // s waits (on the device) for that call's kernels
 int ensure_rebind_meta(gpx_batch* bt);             // pinned n/spec mirrors + dirty flags
+void keep_slot_box(gpx_batch* bt, int b, const double* box);  // remember slot b's X boxes (gpx_api.hip)
+
+// GPX_SUBMIT_STATS: wall-clock phase accumulators of the submit/complete calls (host profiling)
+inline bool submit_stats_on() { return knob_on(Knob::SubmitStats); }
+void print_submit_stats(const gpx_batch* bt);
+struct SubClock {
+  gpx_batch* bt;
+  bool on;
+  std::chrono::steady_clock::time_point t;
+  explicit SubClock(gpx_batch* b) : bt(b), on(submit_stats_on()) {
+    if (on) t = std::chrono::steady_clock::now();
+  }
+  void skip() {
+    if (on) t = std::chrono::steady_clock::now();
+  }
+  void lap(int i) {
+    if (!on) return;
+    const auto n = std::chrono::steady_clock::now();
+    bt->sub_s[i] += std::chrono::duration<double>(n - t).count();
+    t = n;
+  }
+};
 
 }  // namespace gpx
 

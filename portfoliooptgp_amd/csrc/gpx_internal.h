@@ -1,9 +1,10 @@
-// gpx_internal.h — launch arguments and launcher entry points shared by gpx_api.hip and
-// gpx_kernels.hip. Not part of the public ABI (include/gpx.h is).
+// gpx_internal.h — launch arguments and launcher entry points shared by the host files and the
+// kernel files. Not part of the public ABI (include/gpx.h is).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "gpx_kfun.h"
+#include "gpx_knobs.h"  // (the launchers' own switches: GPX_B16_FUSED, GPX_BCR_GRAPH)
 
 namespace gpx {
 

@@ -1,5 +1,5 @@
 """Per-call device timeline of each host process from a wave trace with stream-order markers
-(bench.py GPX_WAVE_TRACE=1 GPX_WAVE_TRACE_OUT=f.npz; markers from gpx_api.hip trace_mark):
+(bench.py GPX_WAVE_TRACE=1 GPX_WAVE_TRACE_OUT=f.npz; markers from gpx_eval.hip trace_mark):
   38 submit reached the device   39 rebind gather done   40 band16 work starts
   43 a lane's K band built       41 lanes joined         42 reduce done   44 results downloaded
 and the band16 waves (kind < 32) between them. Prints the median time of each segment per call
