@@ -32,7 +32,8 @@
  *    they are filled (the L-BFGS-B driver on the host needs them immediately).
  *  - theta is in constrained space (θ > 0), row stride GPX_THETA_STRIDE per problem:
  *    theta[b*GPX_THETA_STRIDE + p] for the kernel parameters p < spec.n_params, followed by the
- *    Gaussian noise variance σn² at p = spec.n_params. grad has the same layout and holds
+ *    Gaussian noise variance σn² at p = spec.n_params (and, for a slot with a mean function, its
+ *    coefficients behind that: gpx_batch_set_mean). grad has the same layout and holds
  *    ∂logML/∂θ (the chain rule to the unconstrained variables is the caller's job).
  *  - Per-term parameter order follows GPflow's tf.Module flattening (sorted attribute names):
  *      SE/Matern12/Matern32/Matern52/Exponential : [lengthscales, variance]
@@ -67,7 +68,7 @@ extern "C" {
 #define GPX_INFO_DEFERRED (-1000)
 
 #define GPX_MAX_TERMS 4
-#define GPX_THETA_STRIDE 16 /* kernel params + 1 noise slot, per problem */
+#define GPX_THETA_STRIDE 16 /* kernel params + 1 noise slot (+ mean coefficients), per problem */
 #define GPX_MAX_DIM 16      /* input dimension D limit */
 
 typedef enum {
@@ -97,6 +98,17 @@ typedef struct {
   int32_t reserved;
   gpx_term terms[GPX_MAX_TERMS];
 } gpx_kernel_spec;
+
+/* Parametric mean function of a GPR problem (gpflow.functions Constant / Linear / Polynomial, one
+ * output column). Its coefficients β sit in the θ row behind the noise slot, theta[n_params + 1 + k]
+ * for k < n_coef, in the order
+ *   CONSTANT   [c]                        m(x) = c                          n_coef = 1
+ *   LINEAR     [A_0 .. A_{D-1}, b]        m(x) = Σ_d x_d A_d + b            n_coef = D + 1
+ *   POLYNOMIAL [w_0 .. w_degree]          m(x) = Σ_k w_k x^k  (D = 1)       n_coef = degree + 1 <= 5
+ * and grad carries ∂logML/∂β_k in the same columns. Coefficients are unconstrained (any finite
+ * value); the row must hold them: n_params + 1 + n_coef <= GPX_THETA_STRIDE. */
+typedef enum { GPX_MEAN_ZERO = 0, GPX_MEAN_CONSTANT = 1, GPX_MEAN_LINEAR = 2, GPX_MEAN_POLYNOMIAL = 3 } gpx_mean_kind;
+typedef struct { int32_t kind, degree, n_coef, reserved; } gpx_mean_spec;
 
 typedef struct gpx_ctx gpx_ctx;
 typedef struct gpx_batch gpx_batch;
@@ -165,6 +177,15 @@ int gpx_batch_rebind_device(gpx_batch* batch, int b, int n, const double* X, con
  * needs no box download (and no stream synchronise) for this slot. */
 int gpx_batch_rebind_device_boxed(gpx_batch* batch, int b, int n, const double* X, const double* Y,
                                   const gpx_kernel_spec* spec, const double* boxes, void* stream);
+/*
+ * The mean function of slot b (NULL or kind GPX_MEAN_ZERO: zero mean, the state of every slot after
+ * creation and after ANY gpx_batch_rebind* of it). With r = y − m(X; β) every evaluation runs on r:
+ * logML and the kernel / noise gradients are the zero-mean formulas on r, ∂logML/∂β_k =
+ * Σ_j α_j ∂m(x_j)/∂β_k, predictions at new inputs gain m(X*), variances do not change. A slot with
+ * kind CONSTANT and c = 0 gives the zero-mean bits. Refused (GPX_BAD_ARG) on band-storage batches,
+ * while deferred completion is on, while an evaluation is submitted, and when the θ row is too short.
+ */
+int gpx_batch_set_mean(gpx_batch* batch, int b, const gpx_mean_spec* mean);
 /* The boxes of slot b's X (layout as above) as computed when its inputs were last gathered;
  * GPX_BAD_ARG if unknown (not gathered yet, host-staged, or no band tables for this batch's
  * shape). For a caller that caches them per series. */
@@ -413,6 +434,13 @@ int gpx_host_theta_rows(int n_fits, int n_vars, const double* u, const int32_t* 
 int gpx_host_loss_grad_u(int n_fits, int n_vars, const double* u, const int32_t* rows,
                          const int32_t* cols, const double* lml, const double* grad, double* loss,
                          double* grad_u);
+/* The same with a transform code per variable, tcode [n_vars]: 0 = softplus + Shift as above,
+ * 1 = identity (θ = u, ∂θ/∂u = 1: the mean-function coefficients; lower[v] is ignored). */
+int gpx_host_theta_rows_t(int n_fits, int n_vars, const double* u, const int32_t* rows,
+                          const int32_t* cols, const double* lower, const int32_t* tcode, double* theta);
+int gpx_host_loss_grad_u_t(int n_fits, int n_vars, const double* u, const int32_t* rows,
+                           const int32_t* cols, const int32_t* tcode, const double* lml, const double* grad,
+                           double* loss, double* grad_u);
 
 #ifdef __cplusplus
 }

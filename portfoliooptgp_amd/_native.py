@@ -19,6 +19,10 @@ GPX_MAX_DIM = 16
 (GPX_SE, GPX_MATERN12, GPX_MATERN32, GPX_MATERN52, GPX_EXPONENTIAL, GPX_RQ, GPX_PERIODIC_SE,
  GPX_LINEAR) = range(1, 9)
 GPX_SUM, GPX_PRODUCT = 0, 1
+# gpx_mean_kind (include/gpx.h)
+GPX_MEAN_ZERO, GPX_MEAN_CONSTANT, GPX_MEAN_LINEAR, GPX_MEAN_POLYNOMIAL = range(4)
+# per-variable transform codes of gpx_host_theta_rows_t / gpx_host_loss_grad_u_t
+TRANSFORM_SOFTPLUS, TRANSFORM_IDENTITY = 0, 1
 # gpx_batch_set_band_route (include/gpx.h)
 BAND_ROUTES = {"sweeps": 0, "bcr": 1, "auto": 2}
 
@@ -41,6 +45,7 @@ EXPORTED_SYMBOLS = (
     "gpx_svgp_create", "gpx_svgp_destroy", "gpx_svgp_partials", "gpx_svgp_bind_partials",
     "gpx_svgp_eval_local", "gpx_svgp_eval_finish", "gpx_svgp_elbo_grad", "gpx_svgp_predict",
     "gpx_host_theta_rows", "gpx_host_loss_grad_u",
+    "gpx_batch_set_mean", "gpx_host_theta_rows_t", "gpx_host_loss_grad_u_t",
 )
 
 
@@ -53,6 +58,11 @@ class GpxKernelSpec(ctypes.Structure):
     _fields_ = [("n_terms", ctypes.c_int32), ("combine", ctypes.c_int32),
                 ("n_params", ctypes.c_int32), ("reserved", ctypes.c_int32),
                 ("terms", GpxTerm * GPX_MAX_TERMS)]
+
+
+class GpxMeanSpec(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("degree", ctypes.c_int32),
+                ("n_coef", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 class GpxTiming(ctypes.Structure):
@@ -219,6 +229,14 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.gpx_host_loss_grad_u.restype = c_int
         lib.gpx_host_loss_grad_u.argtypes = [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_void_p]
+        lib.gpx_batch_set_mean.restype = c_int
+        lib.gpx_batch_set_mean.argtypes = [c_void_p, c_int, ctypes.POINTER(GpxMeanSpec)]
+        lib.gpx_host_theta_rows_t.restype = c_int
+        lib.gpx_host_theta_rows_t.argtypes = [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p]
+        lib.gpx_host_loss_grad_u_t.restype = c_int
+        lib.gpx_host_loss_grad_u_t.argtypes = [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_void_p]
         if path is None:
             _lib = lib
         return lib

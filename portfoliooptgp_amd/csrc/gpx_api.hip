@@ -347,6 +347,9 @@ int gpx_batch_destroy(gpx_batch* bt) {
   if (bt->d_box) (void)hipFree(bt->d_box);
   if (bt->h_nmeta) (void)hipHostFree(bt->h_nmeta);
   if (bt->h_specs) (void)hipHostFree(bt->h_specs);
+  if (bt->resid) (void)hipFree(bt->resid);
+  if (bt->d_mean) (void)hipFree(bt->d_mean);
+  if (bt->h_mean) (void)hipHostFree(bt->h_mean);
   for (int g = 0; g < kAux; ++g)
     if (bt->aux[g]) (void)hipStreamDestroy(bt->aux[g]);
   if (bt->hp) (void)hipStreamDestroy(bt->hp);
@@ -390,6 +393,7 @@ int gpx_batch_rebind(gpx_batch* bt, int b, int n, const gpx_kernel_spec* spec) {
   bt->n[b] = n;
   bt->specs[b] = sp;
   bt->fac_valid[b] = 0;
+  mean_reset_slot(bt, b);  // (every rebind leaves the slot zero-mean: gpx_batch_set_mean)
   bt->fac_band[b] = 0;
   if (!bt->dirty.empty() && bt->dirty[b]) {  // the caller's own device data supersedes a staged one
     bt->dirty[b] = 0;
@@ -455,6 +459,7 @@ int gpx_batch_rebind_device(gpx_batch* bt, int b, int n, const double* X, const 
   bt->n[b] = n;
   bt->specs[b] = *spec;
   bt->fac_valid[b] = 0;
+  mean_reset_slot(bt, b);
   bt->fac_band[b] = 0;
   if (!bt->dirty.empty() && bt->dirty[b]) {  // supersedes a host-staged rebind of the slot
     bt->dirty[b] = 0;
@@ -521,6 +526,7 @@ int gpx_batch_rebind_host(gpx_batch* bt, int b, int n, const double* X, const do
   bt->n[b] = n;
   bt->specs[b] = *spec;
   bt->fac_valid[b] = 0;
+  mean_reset_slot(bt, b);
   bt->fac_band[b] = 0;
   if (!bt->dirty[b]) {
     bt->dirty[b] = 1;
@@ -550,6 +556,8 @@ int gpx_batch_set_deferred(gpx_batch* bt, int q) {
   if (!bt) return GPX_BAD_ARG;
   if (q < 0 && !bt->slow_out.empty())
     return fail(bt->ctx, GPX_BAD_ARG, "deferred evaluations in flight (gpx_batch_deferred_wait first)");
+  if (q >= 0 && bt->n_mean > 0)
+    return fail(bt->ctx, GPX_BAD_ARG, "deferred completion is not supported on a batch with a mean function");
   bt->defer_q = q < 0 ? -1 : q;
   if (bt->deferred.size() != (size_t)bt->B) bt->deferred.assign(bt->B, 0);
   return GPX_OK;

@@ -139,7 +139,7 @@ void alpha_solve(const Run& r) {
   const long long st = mat_stride(bt);
   TrmvArgs t{};
   t.active = r.d_act; t.Wm = bt->W; t.sW = st; t.ld = bt->Np;
-  t.x = bt->Y; t.sx = bt->Nmax; t.nvalid = bt->d_n; t.y = bt->z; t.sy = bt->Np;
+  t.x = eval_y(bt); t.sx = bt->Nmax; t.nvalid = bt->d_n; t.y = bt->z; t.sy = bt->Np;
   t.rows = t.cols = bt->Np; t.lower = 1;
   launch_trmv_n(t, r.na, r.s);
   TrmvArgs u{};
@@ -189,7 +189,7 @@ void small64_eval(const Run& r, bool grad, char* sio, int tag) {
   gpx_batch* bt = r.bt;
   Small64Args a{};
   a.active = r.d_act; a.specs = bt->d_specs; a.theta = bt->d_theta; a.nvalid = bt->d_n;
-  a.X = bt->X; a.sX = (long long)bt->Nmax * bt->D; a.D = bt->D; a.Y = bt->Y; a.sY = bt->Nmax;
+  a.X = bt->X; a.sX = (long long)bt->Nmax * bt->D; a.D = bt->D; a.Y = eval_y(bt); a.sY = bt->Nmax;
   a.W = bt->W; a.sMat = mat_stride(bt); a.ld = bt->Np;
   a.z = bt->z; a.alpha = bt->alpha; a.ldiag = bt->ldiag; a.sVec = bt->Np;
   a.info = bt->d_info; a.results = bt->results; a.grad = grad ? 1 : 0;

@@ -50,7 +50,7 @@ void band_eval(const Run& r, int p, int max_terms) {
   }
   BandSolveArgs sa{};
   sa.active = r.d_act; sa.W = bt->W; sa.L = bt->L; sa.sMat = st; sa.ld = Np;
-  sa.Y = bt->Y; sa.sY = bt->Nmax; sa.nvalid = bt->d_n; sa.z = bt->z; sa.alpha = bt->alpha; sa.sVec = Np;
+  sa.Y = eval_y(bt); sa.sY = bt->Nmax; sa.nvalid = bt->d_n; sa.z = bt->z; sa.alpha = bt->alpha; sa.sVec = Np;
   sa.Np = Np; sa.p = p;
   launch_band_solve(sa, r.na, r.s);
   // backward: selected inversion into K's band blocks (K is dead after the leaves read it)
@@ -177,7 +177,7 @@ BandFusedArgs band_fused_args(const Run& r) {
   BandFusedArgs fa{};
   fa.active = r.d_act; fa.bandp = r.bandp ? r.bandp : bt->d_bandp; fa.K = bt->K; fa.L = bt->L; fa.W = bt->W;
   fa.sMat = mat_stride(bt);
-  fa.Y = bt->Y; fa.sY = bt->Nmax; fa.nvalid = bt->d_n; fa.z = bt->z; fa.alpha = bt->alpha;
+  fa.Y = eval_y(bt); fa.sY = bt->Nmax; fa.nvalid = bt->d_n; fa.z = bt->z; fa.alpha = bt->alpha;
   fa.ldiag = bt->ldiag; fa.sVec = bt->Np; fa.X = bt->X; fa.sX = (long long)bt->Nmax * bt->D; fa.D = bt->D;
   fa.specs = bt->d_specs; fa.theta = r.theta ? r.theta : bt->d_theta; fa.partial = bt->partial;
   fa.sPartial = bt->partial_stride;
@@ -192,7 +192,7 @@ BcrArgs bcr_args(const Run& r, const Lane& l, int qc) {
   gpx_batch* bt = r.bt;
   BcrArgs ca{};
   ca.active = r.d_act + l.off; ca.specs = bt->d_specs; ca.theta = r.theta ? r.theta : bt->d_theta; ca.nvalid = bt->d_n;
-  ca.X = bt->X; ca.sX = (long long)bt->Nmax * bt->D; ca.D = bt->D; ca.Y = bt->Y; ca.sY = bt->Nmax;
+  ca.X = bt->X; ca.sX = (long long)bt->Nmax * bt->D; ca.D = bt->D; ca.Y = eval_y(bt); ca.sY = bt->Nmax;
   ca.sWs = bcr_ws_doubles(qc, bt->Nmax);
   ca.ws = *r.bcr_wsp + l.wso; ca.info = r.info ? r.info : bt->d_info;
   ca.z = bt->z; ca.ldiag = bt->ldiag; ca.alpha = bt->alpha; ca.sVec = bt->Np; ca.Np = bt->Np;
@@ -483,6 +483,10 @@ static int check_active_theta(gpx_batch* bt, int n_active, const int32_t* active
       if (!(v > 0.0) || !std::isfinite(v))
         return fail(ctx, GPX_BAD_ARG, "theta must be finite and > 0 (constrained space)");
     }
+    // (a mean function's coefficients, behind the noise: any finite value, zero and negative too)
+    for (int p = np + 1, e = np + 1 + mean_ncoef(bt, b); p < e; ++p)
+      if (!std::isfinite(theta[(size_t)b * GPX_THETA_STRIDE + p]))
+        return fail(ctx, GPX_BAD_ARG, "mean-function coefficients must be finite");
   }
   return GPX_OK;
 }
@@ -796,7 +800,7 @@ static const char* const kNotPdMessage = "K + noise*I is not positive definite f
 // nothing is written and the caller re-evaluates the row densely (redo_dense).
 static bool deliver_row(gpx_batch* bt, int b, const double* res, int inf, bool band, double band_tol,
                         const double* theta, double* lml, double* grad, int32_t* info, int& status) {
-  const int np = bt->specs[b].n_params;
+  const int np = bt->specs[b].n_params + mean_ncoef(bt, b);  // (the mean's coefficients follow the noise)
   if (band && inf == 0 && !(res[kResBandCheck] <= band_tol)) return false;
   info[b] = inf;
   if (inf != 0) {
@@ -1056,8 +1060,10 @@ int submit_all_shadow(SubmitCall& c) {
 // are the call's whole device round trip (the drop-in pattern's solo calls, VERDICT r05 item 6;
 // GPX_SMALL_DIRECT=0: the DMA'd I/O block)
 bool small_direct_call(const SubmitCall& c) {
+  // (not for a batch with a mean function: its gradient kernel follows the fused launch, whose
+  // polled flag would tell the host to read the results before that kernel has written its columns)
   return knob_on(Knob::SmallDirect) && small64_on(c.bt) && c.rt.n_dense == c.n_active && !c.shadow_async &&
-         c.rt.shadow_ids.empty();
+         c.rt.shadow_ids.empty() && c.bt->n_mean == 0;
 }
 
 int submit_small_direct(SubmitCall& c) {
@@ -1300,12 +1306,18 @@ int gpx_batch_lml_grad_submit(gpx_batch* bt, int n_active, const int32_t* active
   std::unique_ptr<gpx_batch::PendingEval> pe =
       new_pending(c, c.n_active, ctx->profiling != 0, ctx->profiling != 0 && rt.n_dense > 0, ctx->profiling != 0);
   pe->total->mark();
+  if (bt->n_mean > 0) {  // the residuals every route below reads as its targets (eval_y)
+    rc = mean_residuals(bt, bt->d_active, c.n_active, s);
+    if (rc != GPX_OK) return c.drop_shadow(rc);
+  }
   rc = submit_dense(c, *pe);
   if (rc != GPX_OK) return rc;
   pe->bp->mark();
   submit_band_blocks(c);
   rc = submit_fused(c, *pe);
   if (rc != GPX_OK) return rc;
+  // (every route's reduce has written its result rows, on s or joined to it; α is the route's)
+  if (bt->n_mean > 0) mean_gradients(bt, bt->d_active, c.n_active, s);
   pe->bp->mark();
   pe->total->mark();
   HIPX(ctx, hipGetLastError());

@@ -31,6 +31,15 @@ struct gpx_batch {
   const double* Y = nullptr;
   std::vector<int> n;
   std::vector<gpx_kernel_spec> specs;
+  // parametric mean functions (gpx_batch_set_mean, gpx_mean.hip); all empty / null until a slot
+  // gets a non-zero mean. n_mean > 0: every evaluation reads resid (r = y − m(X; β), written at the
+  // start of the call) where it would read Y — see eval_y
+  std::vector<gpx_mean_spec> means;  // [B] once allocated
+  int n_mean = 0;                    // slots with a non-zero mean
+  int mean_dirty = 0;                // means / specs changed since d_mean was uploaded
+  double* resid = nullptr;           // [B][Nmax], allocated once (its pointer stays stable)
+  gpx::DevMean* d_mean = nullptr;    // [B]
+  gpx::DevMean* h_mean = nullptr;    // pinned mirror
   int* d_n = nullptr;
   gpx::DevSpec* d_specs = nullptr;
   double* d_theta = nullptr;
@@ -204,6 +213,16 @@ inline int fail(gpx_ctx* ctx, int code, const std::string& msg) {
 
 inline long long mat_stride(const gpx_batch* bt) { return bt->smat ? bt->smat : (long long)bt->Np * bt->Np; }
 inline int mat_ld(const gpx_batch* bt) { return bt->ldm ? bt->ldm : bt->Np; }
+// the targets an evaluation factorises against, [B][Nmax]: y, or the residual y − m(X; β) of a
+// batch that has a mean function (same stride either way)
+inline const double* eval_y(const gpx_batch* bt) { return bt->n_mean > 0 ? bt->resid : bt->Y; }
+// the batch's mean state (gpx_mean.hip)
+int mean_ncoef(const gpx_batch* bt, int b);      // coefficients behind slot b's noise column (0: zero mean)
+void mean_reset_slot(gpx_batch* bt, int b);      // a rebind: the slot is zero-mean again
+int flush_means(gpx_batch* bt, hipStream_t s);   // the slots' specs to the device when they changed
+int mean_residuals(gpx_batch* bt, const int* d_act, int na, hipStream_t s);  // resid of the listed slots
+void mean_gradients(gpx_batch* bt, const int* d_act, int na, hipStream_t s);  // Φᵀα into their result rows
+void mean_add(gpx_batch* bt, const int* d_act, int na, const double* Xnew, int M, double* mean, hipStream_t s);
 constexpr int kBandStoreP = 2;     // band width (64-blocks) held by band storage
 constexpr int kBox = 16;           // rows per bounding box of the band tables (16: the band16 path's block)
 constexpr int kBand16MaxQ = 8;     // widest band (16-blocks) of the band16 kernels (gpx_band16.hip)

@@ -4,7 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "gpx_kfun.h"
-#include "gpx_knobs.h"  // (the launchers' own switches: GPX_B16_FUSED, GPX_BCR_GRAPH)
+#include "gpx_mean.h"
+#include "gpx_knobs.h" // (the launchers' own switches: GPX_B16_FUSED, GPX_BCR_GRAPH)
 
 namespace gpx {
 
@@ -256,6 +257,23 @@ long long bcr_ws_doubles(int Q, int Nmax);
 // cache: the batch's captured chains (gpx_batch::bcr_graphs; created on first use), or nullptr
 void launch_bcr(const BcrArgs& a, int Q, int max_terms, int np, int Nmax, hipStream_t s, void** cache);
 void bcr_graph_cache_free(void* cache);
+
+// ---- parametric mean functions (gpx_mean.hip) -------------------------------------------------
+// one argument block for the three kernels; each reads the fields its comment names
+struct MeanArgs {
+  const int* active;
+  const DevMean* means;                        // [B] spec + first coefficient column per slot
+  const double* theta;                         // [B][16] device: β_b = theta[b] + means[b].off
+  const int* nvalid;
+  const double* X; long long sX; int D;        // the points: X + b*sX, [rows][D]
+  const double* Y; long long sY;               // resid: the targets
+  double* out; long long sOut; int rows;       // resid: r [B][rows = N_max]; add: mean [B][rows = M]
+  const double* alpha; long long sVec;         // grad: the route's α
+  double* results;                             // grad: [B][kResStride], columns 1 + off + k
+};
+void launch_mean_resid(const MeanArgs& a, int n_active, hipStream_t s);  // r = y − m(X), zero padded
+void launch_mean_grad(const MeanArgs& a, int n_active, hipStream_t s);   // ∂logML/∂β = Σ_j α_j ∂m(x_j)/∂β
+void launch_mean_add(const MeanArgs& a, int n_active, hipStream_t s);    // mean += m(Xnew)
 
 void launch_band_solve(const BandSolveArgs& a, int n_active, hipStream_t s);
 void launch_band_transpose(const BandTransposeArgs& a, int q, int n_active, hipStream_t s);

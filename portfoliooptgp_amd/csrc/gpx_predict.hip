@@ -104,6 +104,10 @@ static int predict_impl(gpx_batch* bt, int n_active, const int32_t* active, cons
   }
   int rc = upload_common(bt, n_active, active, theta, s, true);
   if (rc != GPX_OK) return rc;
+  if (bt->n_mean > 0) {
+    rc = flush_means(bt, s);
+    if (rc != GPX_OK) return rc;
+  }
   // re-factorise the problems whose cached factor is not at exactly this theta. A cached
   // block-banded factorisation (gpx_band.hip) serves predict at the training inputs (it holds
   // α and the diagonal of K⁻¹); any other predict re-factorises densely.
@@ -135,6 +139,10 @@ static int predict_impl(gpx_batch* bt, int n_active, const int32_t* active, cons
     HIPX(ctx, hipMemcpyAsync(bt->d_active, refac.data(), sizeof(int) * refac.size(),
                              hipMemcpyHostToDevice, s));
     const Run rr{bt, bt->d_active, (int)refac.size(), s};
+    if (bt->n_mean > 0) {  // the re-factorised problems' α is solved against y − m(X; β) at this β
+      const int e = mean_residuals(bt, bt->d_active, (int)refac.size(), s);
+      if (e != GPX_OK) return e;
+    }
     if (small64_on(bt)) {
       small64_eval(rr, false);
     } else {
@@ -149,6 +157,8 @@ static int predict_impl(gpx_batch* bt, int n_active, const int32_t* active, cons
   if (train) {
     TrainPredArgs ta{};
     ta.active = bt->d_active; ta.W = bt->W; ta.sW = mat_stride(bt); ta.ld = Np;
+    // (the original targets, with a mean function too: α then solves the residual, and
+    // y − σn²α = m(X) + (r − σn²α) is already the mean of f at the training inputs)
     ta.alpha = bt->alpha; ta.sVec = Np; ta.Y = bt->Y; ta.sY = bt->Nmax; ta.nvalid = bt->d_n;
     ta.specs = bt->d_specs; ta.theta = bt->d_theta; ta.add_noise = add_noise;
     ta.mean = mean; ta.var = var; ta.sOut = bt->Nmax;
@@ -187,6 +197,8 @@ static int predict_impl(gpx_batch* bt, int n_active, const int32_t* active, cons
   t.active = bt->d_active; t.Wm = kxs; t.sW = skx; t.ld = Mp; t.x = bt->alpha; t.sx = Np;
   t.nvalid = nullptr; t.y = mean; t.sy = M; t.rows = Np; t.cols = M; t.lower = 0;
   launch_trmv_t(t, n_active, s);
+  // + m(X*) (the variances below are the zero-mean model's on the residual data)
+  if (bt->n_mean > 0) mean_add(bt, bt->d_active, n_active, Xnew, M, mean, s);
   if (cov) {
     // A = W · Kxs stored; cov = K(X*,X*) − AᵀA (padded rows/cols of A are exactly zero)
     double* abuf;

@@ -184,6 +184,7 @@ class Engine:
         self._rb_cache = {}
         self._streams = {}
         self._box_want = {}  # slot -> (box key, X) of a device rebind whose boxes are not cached yet
+        self._means = {}  # slot -> (kind, degree, n_coef) of its mean function (absent: zero mean)
 
     def __del__(self):
         h = getattr(self, "handle", None)
@@ -346,6 +347,26 @@ class Engine:
         if rc != N.GPX_OK:
             raise N.GPXError(f"gpx_batch_set_band_route failed ({rc}): {self.ctx.last_error()}")
         self.band_route = route
+
+    @property
+    def has_mean(self) -> bool:
+        """Some slot has a non-zero mean function (set_mean)."""
+        return bool(self._means)
+
+    def set_mean(self, b: int, spec: Optional[N.GpxMeanSpec]) -> None:
+        """Slot b's mean function (include/gpx.h gpx_batch_set_mean; None: zero mean). Its
+        coefficients are columns n_params + 1 .. of the slot's θ row. Every rebind of the slot
+        resets it to zero mean, so callers that reuse slots set it after each rebind."""
+        key = None if spec is None or spec.kind == N.GPX_MEAN_ZERO else (spec.kind, spec.degree, spec.n_coef)
+        if self._means.get(b) == key:
+            return
+        rc = self.lib.gpx_batch_set_mean(self.handle, int(b), ctypes.byref(spec) if key is not None else None)
+        if rc != N.GPX_OK:
+            raise N.GPXError(f"gpx_batch_set_mean failed ({rc}): {self.ctx.last_error()}")
+        if key is None:
+            self._means.pop(b, None)
+        else:
+            self._means[b] = key
 
     deferral = -1
 
@@ -539,6 +560,7 @@ class Engine:
         self.specs[b] = spec
         self.n_params[b] = spec.n_params
         self.n[b] = n
+        self._means.pop(b, None)  # (the library resets a rebound slot to zero mean)
         if box is not None:
             rc = self.lib.gpx_batch_rebind_device_boxed(
                 self.handle, int(b), int(n), ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(y.data_ptr()),
@@ -570,6 +592,8 @@ class Engine:
         self.specs[b] = spec
         self.n_params[b] = spec.n_params
         self.n[b] = n
+        if self._means:
+            self._means.pop(b, None)
         if box is not None:
             rc = self.lib.gpx_batch_rebind_device_boxed(self.handle, int(b), int(n), ctypes.c_void_p(x.data_ptr()),
                                                         ctypes.c_void_p(y.data_ptr()), ctypes.byref(spec),
@@ -761,6 +785,10 @@ def solo_engine(model) -> Engine:
     owner = eng._owner() if eng._owner is not None else None
     if owner is not model:
         eng.rebind(0, X, Y, model._spec)
+        # (the rebind left the slot zero-mean, whatever the previous model had)
+        ms = model.mean_spec() if hasattr(model, "mean_spec") else None
+        if ms is not None:
+            eng.set_mean(0, ms)
         eng._owner = weakref.ref(model)
     model._solo_cache = (weakref.ref(eng), _DEFAULT_BAND_ROUTE, key)
     return eng

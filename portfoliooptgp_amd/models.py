@@ -23,17 +23,20 @@ from . import _native as N
 from .engine import Engine, default_device, solo_engine
 from .kernels import Kernel, compile_spec
 from .likelihoods import Gaussian
-from .parameter import Parameter
+from .mean_functions import MeanFunction, Zero
+from .parameter import ArrayParameter, Parameter
 
 
 class GPR:
-    """Exact GP regression with a Gaussian likelihood and a zero mean function."""
+    """Exact GP regression with a Gaussian likelihood and a zero or parametric mean function
+    (mean_functions.Constant / Linear / Polynomial: the device factorises against y − m(X; β))."""
 
     def __init__(self, data: Tuple, kernel: Kernel, mean_function=None,
                  noise_variance: Optional[float] = None, likelihood: Optional[Gaussian] = None,
                  device: Optional[int] = None):
-        if mean_function is not None:
-            raise NotImplementedError("only the zero mean function (GPflow default) is supported")
+        if mean_function is not None and not isinstance(mean_function, MeanFunction):
+            raise NotImplementedError("mean_function must be one of portfoliooptgp_amd.mean_functions "
+                                      "(Zero, Constant, Linear, Polynomial) or None")
         X, Y = data
         self._out_cpu = not (isinstance(Y, torch.Tensor) and Y.is_cuda)
         Xt = X if isinstance(X, torch.Tensor) else torch.as_tensor(np.asarray(X, dtype=np.float64))
@@ -59,18 +62,27 @@ class GPR:
         elif noise_variance is not None:
             raise ValueError("give either noise_variance or likelihood")
         self.likelihood = likelihood
-        self.mean_function = None
+        # (Zero() is kept as given; it has no parameters and the device treats it as no mean)
+        self.mean_function = mean_function
         self.num_latent_gps = 1
         self.device = default_device() if device is None else int(device)
         self._spec = compile_spec(kernel, Xt.shape[1])
+        self._mean = mean_function if mean_function is not None and mean_function.n_coef > 0 else None
+        if self._mean is not None:
+            self._mean._check_dim(int(Xt.shape[1]))
+            if self._spec.n_params + 1 + self._mean.n_coef > N.GPX_THETA_STRIDE:
+                raise ValueError(
+                    f"the θ row holds {N.GPX_THETA_STRIDE} values: {self._spec.n_params} kernel parameters + the "
+                    f"noise variance + {self._mean.n_coef} mean coefficients do not fit")
         self._engine: Optional[Engine] = None
         self._engine_index = 0
 
     # ---------------------------------------------------------------- structure -------
     @property
     def parameters(self) -> Tuple[Parameter, ...]:
-        # GPR attributes sorted: kernel < likelihood (< mean_function, which has none here)
-        return tuple(self.kernel.parameters) + tuple(self.likelihood.parameters)
+        # GPR attributes sorted: kernel < likelihood < mean_function
+        return (tuple(self.kernel.parameters) + tuple(self.likelihood.parameters)
+                + (tuple(self._mean.parameters) if self._mean is not None else ()))
 
     @property
     def trainable_parameters(self) -> Tuple[Parameter, ...]:
@@ -82,24 +94,36 @@ class GPR:
 
     def _param_paths(self):
         return ([("GPR.kernel." + n if n else "GPR.kernel", p) for n, p in self.kernel._param_paths("")]
-                + [("GPR.likelihood.variance", self.likelihood.variance)])
+                + [("GPR.likelihood.variance", self.likelihood.variance)]
+                + ([("GPR.mean_function." + n, p) for n, p in self._mean._param_paths()]
+                   if self._mean is not None else []))
 
     @property
     def n_kernel_params(self) -> int:
         return int(self._spec.n_params)
 
     def theta_row(self) -> np.ndarray:
-        """Constrained θ in the gpx layout: kernel params, then σn² at index n_params."""
+        """Constrained θ in the gpx layout: kernel params, then σn² at index n_params, then the
+        mean function's coefficients (gpx_mean_spec order)."""
         row = np.ones(N.GPX_THETA_STRIDE, dtype=np.float64)
         kp = self.kernel.parameters
         for i, p in enumerate(kp):
             row[i] = p.value
         row[len(kp)] = self.likelihood.variance.value
+        if self._mean is not None:
+            c = self._mean.coefficients()
+            row[len(kp) + 1: len(kp) + 1 + len(c)] = c
         return row
+
+    def mean_spec(self):
+        """The slot's gpx_mean_spec (None: zero mean)."""
+        return self._mean.spec() if self._mean is not None else None
 
     # ---------------------------------------------------------------- engine ----------
     def _attach(self, engine: Engine, index: int) -> None:
         self._engine, self._engine_index = engine, index
+        if self._mean is not None or getattr(engine, "has_mean", False):
+            engine.set_mean(index, self.mean_spec())
 
     def engine(self) -> Tuple[Engine, int]:
         """(engine, slot): the batch engine this model was attached to, else a pooled
@@ -142,29 +166,49 @@ class GPR:
         return closure
 
     def _variable_map(self, variables):
-        """(variables, θ-row index of each variable, its Parameter), cached for the variables
-        object an optimiser passes on every call (kernel parameters, then σn² at n_params)."""
+        """(variables, θ-row index of each flattened variable entry, its Parameter), cached for
+        the variables object an optimiser passes on every call (kernel parameters, then σn² at
+        n_params, then the mean function's coefficients). An array variable (a mean parameter)
+        takes one consecutive column per entry, so ``rows`` follows the optimiser's flattened x."""
         cache = getattr(self, "_grad_map", None)
         if cache is None or cache[0] is not variables:
             pindex = {id(p): i for i, p in enumerate(self.kernel.parameters)}
             nk = len(self.kernel.parameters)
-            rows = []
+            mindex, o = {}, nk + 1
+            for p in (self._mean.parameters if self._mean is not None else ()):
+                mindex[id(p)] = (o, int(np.prod(p.shape)))
+                o += mindex[id(p)][1]
+            rows, params = [], []
             for v in variables:
                 p = v._param
                 if p is self.likelihood.variance:
                     rows.append(nk)
+                    params.append(p)
                 elif id(p) in pindex:
                     rows.append(pindex[id(p)])
+                    params.append(p)
+                elif id(p) in mindex:
+                    c0, cnt = mindex[id(p)]
+                    rows.extend(range(c0, c0 + cnt))
+                    params.extend([p] * cnt)
                 else:
                     raise ValueError(f"variable {v.name} is not a parameter of this model")
-            cache = self._grad_map = (variables, rows, [v._param for v in variables])
+            cache = self._grad_map = (variables, rows, params)
         return cache
 
-    def theta_layout(self, variables):
-        """(cols int32 [P], lower float64 [P]): θ-row index and Shift of each variable, for the
-        batched driver's native θ / chain-rule helpers (gpx_host_theta_rows / _loss_grad_u)."""
+    def theta_layout(self, variables, transforms: bool = False):
+        """(cols int32 [P], lower float64 [P]): θ-row index and Shift of each flattened variable
+        entry, for the batched driver's native θ / chain-rule helpers (gpx_host_theta_rows /
+        _loss_grad_u). With ``transforms`` a third array, int32 [P]: the entry's transform code
+        (0 softplus + Shift, 1 identity: a mean coefficient; gpx_host_theta_rows_t)."""
         _, rows, params = self._variable_map(variables)
-        return (np.asarray(rows, dtype=np.int32), np.asarray([p.lower for p in params], dtype=np.float64))
+        cols = np.asarray(rows, dtype=np.int32)
+        ident = [isinstance(p, ArrayParameter) for p in params]
+        lower = np.asarray([0.0 if i else p.lower for p, i in zip(params, ident)], dtype=np.float64)
+        if not transforms:
+            return cols, lower
+        return cols, lower, np.asarray([N.TRANSFORM_IDENTITY if i else N.TRANSFORM_SOFTPLUS for i in ident],
+                                       dtype=np.int32)
 
     def loss_and_grad_unconstrained(self, variables=None, lml=None, grad_theta=None):
         """(−logML, ∂(−logML)/∂u) for ``variables`` (default: trainable_variables)."""
@@ -174,7 +218,8 @@ class GPR:
         _, rows, params = self._variable_map(variables)
         g = np.empty(len(rows), dtype=np.float64)
         for k, (r, p) in enumerate(zip(rows, params)):
-            g[k] = -grad_theta[r] * p.dtheta_du()
+            # (a mean coefficient's transform is the identity: ∂θ/∂u = 1)
+            g[k] = -grad_theta[r] if isinstance(p, ArrayParameter) else -grad_theta[r] * p.dtheta_du()
         return -float(lml), g
 
     # ---------------------------------------------------------------- prediction ------

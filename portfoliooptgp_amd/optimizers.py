@@ -73,7 +73,9 @@ class ModelStream(Sequence):
             raise IndexError(i)
         m = self._built[i]
         if m is None:
-            m = self._built[i] = self._factory(i)
+            m = self._factory(i)
+            _refuse_streamed_mean(m, i)  # (before the model reaches a device slot)
+            self._built[i] = m
         return m
 
     def build_ahead(self) -> bool:
@@ -106,6 +108,15 @@ def _resolve_model(closure):
                         "(or training_loss_closure()); gradients come from the GPU engine, "
                         "there is no autodiff of arbitrary Python closures")
     return m
+
+
+def _refuse_streamed_mean(model, i) -> None:
+    """minimize_stream rebinds slots between fits and runs with deferred completion and band
+    storage, none of which carries a mean function (include/gpx.h gpx_batch_set_mean)."""
+    if getattr(model, "mean_spec", None) is not None and model.mean_spec() is not None:
+        raise NotImplementedError(
+            f"minimize_stream does not support mean functions (model {i}: GPR with "
+            f"{type(model.mean_function).__name__}); fit it with Scipy().minimize or minimize_batch")
 
 
 def _not_pd_policy(on_not_pd: str):
@@ -354,6 +365,8 @@ class Scipy:
         lazy = isinstance(models, ModelStream)
         if not lazy:
             models = list(models)
+            for i, m in enumerate(models):  # (a ModelStream's models are checked as they are built)
+                _refuse_streamed_mean(m, i)
         if len(models) == 0:
             return [], ([] if predict_train else None)
         width = max(1, min(int(width), len(models)))
@@ -905,13 +918,21 @@ class _SteppedDriver:
         if not variables:
             raise ValueError("model has no trainable variables")
         cols, lower = m.theta_layout(variables)
+        # a layout with an identity variable (a mean-function coefficient) carries its transform
+        # codes and takes the _t host helpers; every other layout keeps the softplus-only ones
+        tcode = None
+        if getattr(m, "mean_function", None) is not None:
+            tc = m.theta_layout(variables, transforms=True)[2]
+            if tc.any():
+                tcode = tc
         # the slot's θ row: fixed parameters now, the trainable columns rewritten every round
         self._theta_of(eng)[row] = m.theta_row()
         x0 = _pack(variables)
         native = gs is not None and self.native
         st = gs.batch(self, len(x0)).start(row, x0) if native else lbfgsb.LbfgsbStepper(x0, self.options)
-        return {"i": i, "m": m, "v": variables, "st": st, "native": native,
-                "cols": cols, "lower": lower, "key": (len(cols), cols.tobytes(), lower.tobytes())}
+        return {"i": i, "m": m, "v": variables, "st": st, "native": native, "tcode": tcode,
+                "cols": cols, "lower": lower,
+                "key": (len(cols), cols.tobytes(), lower.tobytes(), None if tcode is None else tcode.tobytes())}
 
     def _theta_of(self, eng) -> np.ndarray:
         th = self._theta.get(id(eng))
@@ -999,8 +1020,13 @@ class _SteppedDriver:
                     U = np.array([active[r]["st"].x if active[r].get("reeval") is None else active[r]["reeval"]
                                   for r in rs], dtype=np.float64).reshape(len(rs), P)
                 if not moved:
-                    lib.gpx_host_theta_rows(len(rs), P, U.ctypes.data, R.ctypes.data, s0["cols"].ctypes.data,
-                                            s0["lower"].ctypes.data, gs.theta.ctypes.data)
+                    if s0["tcode"] is None:
+                        lib.gpx_host_theta_rows(len(rs), P, U.ctypes.data, R.ctypes.data, s0["cols"].ctypes.data,
+                                                s0["lower"].ctypes.data, gs.theta.ctypes.data)
+                    else:
+                        lib.gpx_host_theta_rows_t(len(rs), P, U.ctypes.data, R.ctypes.data, s0["cols"].ctypes.data,
+                                                  s0["lower"].ctypes.data, s0["tcode"].ctypes.data,
+                                                  gs.theta.ctypes.data)
                 gs.packs.append((rs, P, U, R, s0["cols"]))
             if moved or not self.wide or not self._migrate(gs):
                 break
@@ -1091,8 +1117,14 @@ class _SteppedDriver:
         for rs, P, U, R, cols in gs.packs:
             loss = np.empty(len(rs))
             gu = np.empty((len(rs), P))
-            lib.gpx_host_loss_grad_u(len(rs), P, U.ctypes.data, R.ctypes.data, cols.ctypes.data,
-                                     lml.ctypes.data, grad.ctypes.data, loss.ctypes.data, gu.ctypes.data)
+            tcode = active[rs[0]]["tcode"]  # (one layout per pack)
+            if tcode is None:
+                lib.gpx_host_loss_grad_u(len(rs), P, U.ctypes.data, R.ctypes.data, cols.ctypes.data,
+                                         lml.ctypes.data, grad.ctypes.data, loss.ctypes.data, gu.ctypes.data)
+            else:
+                lib.gpx_host_loss_grad_u_t(len(rs), P, U.ctypes.data, R.ctypes.data, cols.ctypes.data,
+                                           tcode.ctypes.data, lml.ctypes.data, grad.ctypes.data, loss.ctypes.data,
+                                           gu.ctypes.data)
             rest = range(len(rs))
             if active[rs[0]]["native"]:
                 rest = self._tell_native(gs, P, R, U, loss, gu, info, done)
