@@ -420,6 +420,34 @@ int gpx_svgp_predict(gpx_svgp* svgp, const double* theta, const double* Z, const
                      double* var, int32_t* info, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * SGPR: gpflow.models.SGPR((X, Y), kernel, inducing_variable=Z, noise_variance=...) — the
+ * collapsed (Titsias) bound of sparse GP regression with a Gaussian likelihood, zero mean, one
+ * output; test_scripts/SVGP.py:395-412 (SE kernel, M = 10, N ≈ 113).
+ *   gpx_sgpr_elbo_grad  <- model.training_loss value + gradient, fed to
+ *                          gpflow.optimizers.Scipy().minimize(model.training_loss, ...)
+ *   gpx_sgpr_predict    <- model.predict_f(X_test) / predict_y
+ * X [N, D] and Y [N] are device-resident fp64 and caller-owned; they must outlive the object.
+ * Per evaluation (host): theta [16] = kernel params (gpx_kernel_spec layout) then σn² at
+ * theta[n_params]; Z [M, D] row-major. Outputs (host): elbo; grad_theta [16] (∂F/∂θ constrained,
+ * σn² at n_params); grad_Z [M, D].
+ * Two M x M factorisations run per call, so info points to TWO int32: info[0] the first failing
+ * pivot (1-based, 0 = ok) of Kmm = k(Z,Z) + 1e-6 I, info[1] that of B = I + L⁻¹ Kmn Kmnᵀ L⁻ᵀ/σn²
+ * (I + PSD: a failure there means a non-finite input). Either one returns GPX_NOT_PD.
+ * Not provided: mean functions, multi-output Y, full_cov, upper_bound, other likelihoods (VGP /
+ * StudentT), and row-sharding over GPUs — K̄mn depends on the all-reduced B, so shards would need
+ * a two-pass protocol that gpx_svgp_partials does not give.
+ */
+typedef struct gpx_sgpr gpx_sgpr;
+int gpx_sgpr_create(gpx_ctx* ctx, int N, int M, int D, const double* X, const double* Y,
+                    const gpx_kernel_spec* spec, gpx_sgpr** out);
+int gpx_sgpr_destroy(gpx_sgpr* sgpr);
+int gpx_sgpr_elbo_grad(gpx_sgpr* sgpr, const double* theta, const double* Z, double* elbo,
+                       double* grad_theta, double* grad_Z, int32_t* info, void* stream);
+/* predict_f (add_noise = 0) / predict_y (1) at Xnew (device [Mn, D]) -> mean, var (device [Mn]) */
+int gpx_sgpr_predict(gpx_sgpr* sgpr, const double* theta, const double* Z, const double* Xnew, int Mn,
+                     int add_noise, double* mean, double* var, int32_t* info, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Host helpers of the batched L-BFGS-B driver (no device work): for the n_fits fits of one
  * round, u [n_fits, n_vars] are the unconstrained variables (gpflow.optimizers.Scipy's x,
  * GPR/model_trainer.py:18-19), rows [n_fits] their batch slots, cols [n_vars] the θ index of each

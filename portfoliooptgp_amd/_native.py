@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = (
     "gpx_batch_set_band_route",
     "gpx_svgp_create", "gpx_svgp_destroy", "gpx_svgp_partials", "gpx_svgp_bind_partials",
     "gpx_svgp_eval_local", "gpx_svgp_eval_finish", "gpx_svgp_elbo_grad", "gpx_svgp_predict",
+    "gpx_sgpr_create", "gpx_sgpr_destroy", "gpx_sgpr_elbo_grad", "gpx_sgpr_predict",
     "gpx_host_theta_rows", "gpx_host_loss_grad_u",
     "gpx_batch_set_mean", "gpx_host_theta_rows_t", "gpx_host_loss_grad_u_t",
 )
@@ -224,6 +225,17 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.gpx_svgp_predict.restype = c_int
         lib.gpx_svgp_predict.argtypes = [c_void_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                          c_void_p, c_int, c_int, c_void_p, c_void_p, c_int_p, c_void_p]
+        lib.gpx_sgpr_create.restype = c_int
+        lib.gpx_sgpr_create.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, spec_p,
+                                        ctypes.POINTER(c_void_p)]
+        lib.gpx_sgpr_destroy.restype = c_int
+        lib.gpx_sgpr_destroy.argtypes = [c_void_p]
+        lib.gpx_sgpr_elbo_grad.restype = c_int
+        lib.gpx_sgpr_elbo_grad.argtypes = [c_void_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                           c_double_p, c_int_p, c_void_p]
+        lib.gpx_sgpr_predict.restype = c_int
+        lib.gpx_sgpr_predict.argtypes = [c_void_p, c_double_p, c_double_p, c_void_p, c_int, c_int,
+                                         c_void_p, c_void_p, c_int_p, c_void_p]
         lib.gpx_host_theta_rows.restype = c_int
         lib.gpx_host_theta_rows.argtypes = [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
         lib.gpx_host_loss_grad_u.restype = c_int

@@ -364,4 +364,40 @@ void launch_diag_add(double* A, int ld, int n, double v, hipStream_t s);
 void launch_symmetrize_lower(double* A, int ld, int n, hipStream_t s);
 void launch_svgp_predvar(const SvgpPredVarArgs& a, hipStream_t s);
 
+// ---- SGPR (gpx_sgpr.hip; kernels beside the SVGP ones in gpx_svgp_kernels.hip) ---------
+// One pass over the N data rows; block partials [blocks][kResidW] in ResidArgs' layout:
+// 0..15 k̄_nn Σ ∂k_jj/∂θ with k̄_nn = −1/(2σ²) (θ layout), 16 Σ y², 17 Σ k_jj.
+struct SgprDiagArgs {
+  const double* X; const double* Y; int D; int n;
+  const DevSpec* spec; const double* theta;
+  double* part;            // [sgpr_diag_blocks(n)][kResidW]
+};
+// part[c][i] = Σ_{j in column chunk c} A[i][j] x[j], i < rows (a multiple of 16), j < cols
+struct SgprRowDotArgs {
+  const double* A; int ld; int rows; int cols;
+  const double* x;
+  double* part;            // [sgpr_rowdot_chunks(cols)][rows]
+};
+// B = I + Ĝ/s on the leading m×m block, the identity beyond it (all np×np entries written)
+struct SgprBmatArgs {
+  const double* Gh; int ld; int m; int np; double s;
+  double* B;
+};
+// M×M tail after B's factorisation (valid i, j < m; nothing else is written):
+//   H   = (I − B⁻¹)/s − γγᵀ/s³,   Mid = ½(I − B⁻¹) − γγᵀ/(2s²) − Ĝ/(2s)
+// block partials [blocks][4]: tr(Ĝ), Σ B⁻¹∘Ĝ, γᵀĜγ, âᵀγ
+struct SgprFinalArgs {
+  const double* Binv; const double* Gh; const double* gam; const double* ahat; double s;
+  int m, ld;
+  double* H; double* Mid; double* part;
+};
+void launch_sgpr_diag(const SgprDiagArgs& a, hipStream_t s);
+int sgpr_diag_blocks(int n);
+void launch_sgpr_rowdot(const SgprRowDotArgs& a, hipStream_t s);
+int sgpr_rowdot_chunks(int cols);
+void launch_sgpr_bmat(const SgprBmatArgs& a, hipStream_t s);
+void launch_sgpr_final(const SgprFinalArgs& a, hipStream_t s);
+int sgpr_final_blocks(int m);
+void launch_vscale(const double* x, double* y, int n, double c, hipStream_t s);  // y = c x
+
 }  // namespace gpx

@@ -1,5 +1,5 @@
-// gpx_svgp_kernels.hip — device kernels of the SVGP ELBO path that are
-// not GEMMs. The M²N work (G = Kmn Kmnᵀ, Y = 2c·P·Kmn) runs on the MFMA GEMM of
+// gpx_svgp_kernels.hip — device kernels of the SVGP ELBO path and of the
+// SGPR collapsed bound (gpx_sgpr.hip, the section at the end) that are not GEMMs. The M²N work (G = Kmn Kmnᵀ, Y = 2c·P·Kmn) runs on the MFMA GEMM of
 // gpx_kernels.hip; what is here is O(MN) element work: kernel-derivative contractions
 // (exp-bound, one pass over Y and X), the residual / k_diag sums, split-K reductions and the
 // O(M²) elementwise tail. All HBM streams are coalesced along the N (data) axis.
@@ -248,7 +248,141 @@ __global__ __launch_bounds__(256) void svgp_predvar_kernel(SvgpPredVarArgs a) {
   a.var[j] = v;
 }
 
+// ---- SGPR ------------------------------------------------------------------------------
+// The N-row pass of the collapsed bound: Σ y², Σ k_jj and k̄_nn Σ ∂k_jj/∂θ. One thread per row,
+// X staged through LDS so the [n][D] stream is coalesced.
+__global__ __launch_bounds__(256) void sgpr_diag_kernel(SgprDiagArgs a) {
+  __shared__ double sx[256 * GPX_MAX_DIM];
+  __shared__ double sth[GPX_THETA_STRIDE];
+  __shared__ double sred[4 * kResidW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int j0 = blockIdx.x * 256, D = a.D;
+  for (int e = tid; e < 256 * D; e += 256) {
+    const int j = j0 + e / D;
+    sx[e] = j < a.n ? a.X[(long long)j0 * D + e] : 0.0;
+  }
+  if (tid < GPX_THETA_STRIDE) sth[tid] = a.theta[tid];
+  __syncthreads();
+  const DevSpec spec = *a.spec;
+  const double c = -0.5 / sth[spec.n_params];
+  const int j = j0 + tid;
+  double sums[GPX_MAX_TERMS][3];
+#pragma unroll
+  for (int t = 0; t < GPX_MAX_TERMS; ++t) sums[t][0] = sums[t][1] = sums[t][2] = 0.0;
+  double sq = 0.0, kd = 0.0;
+  if (j < a.n) {
+    const double y = a.Y[j];
+    sq = y * y;
+    double dk[GPX_MAX_TERMS][3];
+    kd = eval_k_grad<GPX_MAX_TERMS>(spec, sth, sx + tid * D, sx + tid * D, dk);
+#pragma unroll
+    for (int t = 0; t < GPX_MAX_TERMS; ++t) {
+      sums[t][0] = c * dk[t][0]; sums[t][1] = c * dk[t][1]; sums[t][2] = c * dk[t][2];
+    }
+  }
+  double* out = a.part + (long long)blockIdx.x * kResidW;
+  const double vsq = wsum(sq), vkd = wsum(kd);
+  if (lane == 0) { sred[wave * 2] = vsq; sred[wave * 2 + 1] = vkd; }
+  __syncthreads();
+  double s_sq = 0.0, s_kd = 0.0;
+  if (tid == 0) {
+    for (int w = 0; w < 4; ++w) { s_sq += sred[w * 2]; s_kd += sred[w * 2 + 1]; }
+  }
+  __syncthreads();
+  reduce_theta(sums, a.spec, sred, out);
+  if (tid == 0) { out[16] = s_sq; out[17] = s_kd; out[18] = 0.0; out[19] = 0.0; }
+}
+
+// w = Kmn y as chunk partials: a workgroup takes 16 rows x kRowDotChunk columns, each wave four
+// rows at once (four independent coalesced row streams in flight per lane), so the M x N stream
+// is spread over (M/16) x (N/chunk) workgroups instead of M/64 long-row ones.
+constexpr int kRowDotChunk = 4096;
+__global__ __launch_bounds__(256) void sgpr_rowdot_kernel(SgprRowDotArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i0 = blockIdx.x * 16 + wave * 4;      // rows is a multiple of 16: i0 + 3 < rows
+  const int c0 = blockIdx.y * kRowDotChunk;
+  const int c1 = min(c0 + kRowDotChunk, a.cols);
+  const double* r = a.A + (long long)i0 * a.ld;
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+  for (int j = c0 + lane; j < c1; j += 64) {
+    const double xv = a.x[j];
+    const double m0 = r[j], m1 = r[(long long)a.ld + j], m2 = r[2LL * a.ld + j], m3 = r[3LL * a.ld + j];
+    s0 = fma(m0, xv, s0); s1 = fma(m1, xv, s1); s2 = fma(m2, xv, s2); s3 = fma(m3, xv, s3);
+  }
+  s0 = wsum(s0); s1 = wsum(s1); s2 = wsum(s2); s3 = wsum(s3);
+  if (lane == 0) {
+    double* out = a.part + (long long)blockIdx.y * a.rows + i0;
+    out[0] = s0; out[1] = s1; out[2] = s2; out[3] = s3;
+  }
+}
+
+__global__ __launch_bounds__(256) void sgpr_bmat_kernel(SgprBmatArgs a) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int i = (int)(e / a.np), j = (int)(e - (long long)(e / a.np) * a.np);
+  if (i >= a.np) return;
+  const double d = (i == j) ? 1.0 : 0.0;
+  a.B[(long long)i * a.np + j] = (i < a.m && j < a.m) ? d + a.Gh[(long long)i * a.ld + j] / a.s : d;
+}
+
+__global__ __launch_bounds__(256) void sgpr_final_kernel(SgprFinalArgs a) {
+  __shared__ double sred[4][4];
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int i = (int)(e / a.m), j = (int)(e - (long long)(e / a.m) * a.m);
+  double v[4] = {0.0, 0.0, 0.0, 0.0};
+  if (i < a.m) {
+    const long long o = (long long)i * a.ld + j;
+    const double s = a.s, gh = a.Gh[o], bi = a.Binv[o];
+    const double gg = a.gam[i] * a.gam[j];
+    const double imb = ((i == j) ? 1.0 : 0.0) - bi;
+    a.H[o] = imb / s - gg / (s * s * s);
+    a.Mid[o] = 0.5 * imb - gg / (2.0 * s * s) - gh / (2.0 * s);
+    v[1] = bi * gh;
+    v[2] = gg * gh;
+    if (i == j) { v[0] = gh; v[3] = a.ahat[i] * a.gam[i]; }
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const double t = wsum(v[q]);
+    if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6][q] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x < 4)
+    a.part[(long long)blockIdx.x * 4 + threadIdx.x] =
+        (sred[0][threadIdx.x] + sred[1][threadIdx.x]) + (sred[2][threadIdx.x] + sred[3][threadIdx.x]);
+}
+
+__global__ void vscale_kernel(const double* x, double* y, int n, double c) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) y[i] = c * x[i];
+}
+
 }  // namespace
+
+int sgpr_diag_blocks(int n) { return (n + 255) / 256; }
+
+void launch_sgpr_diag(const SgprDiagArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(sgpr_diag_kernel, dim3(sgpr_diag_blocks(a.n)), dim3(256), 0, s, a);
+}
+
+int sgpr_rowdot_chunks(int cols) { return (cols + kRowDotChunk - 1) / kRowDotChunk; }
+
+void launch_sgpr_rowdot(const SgprRowDotArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(sgpr_rowdot_kernel, dim3(a.rows / 16, sgpr_rowdot_chunks(a.cols)), dim3(256), 0, s, a);
+}
+
+void launch_sgpr_bmat(const SgprBmatArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(sgpr_bmat_kernel, dim3((unsigned)(((long long)a.np * a.np + 255) / 256)), dim3(256), 0, s, a);
+}
+
+int sgpr_final_blocks(int m) { return (int)(((long long)m * m + 255) / 256); }
+
+void launch_sgpr_final(const SgprFinalArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(sgpr_final_kernel, dim3(sgpr_final_blocks(a.m)), dim3(256), 0, s, a);
+}
+
+void launch_vscale(const double* x, double* y, int n, double c, hipStream_t s) {
+  hipLaunchKernelGGL(vscale_kernel, dim3((n + 255) / 256), dim3(256), 0, s, x, y, n, c);
+}
 
 int rows_chunk_for(int D) {
   const int dm = D <= 1 ? 1 : D <= 2 ? 2 : D <= 4 ? 4 : D <= 8 ? 8 : 16;

@@ -746,6 +746,89 @@ class SVGPEngine:
         return mean, var
 
 
+class SGPREngine:
+    """Device state of one SGPR model (include/gpx.h gpx_sgpr): X [N, D] / Y [N] resident in
+    HBM, Kmn and the two M x M factorisations' workspace owned by the library."""
+
+    def __init__(self, X, Y, spec: N.GpxKernelSpec, M: int, device: Optional[int] = None):
+        self.device = require_gpu(device)
+        self.ctx = N.Context.get(self.device)
+        self.lib = self.ctx.lib
+        x = to_device_f64(X, self.device)
+        self.X = x.reshape(x.shape[0], -1).contiguous()
+        self.Y = to_device_f64(Y, self.device).reshape(-1).contiguous()
+        self.N, self.D = self.X.shape
+        if self.Y.shape[0] != self.N:
+            raise ValueError("X and Y must have the same number of rows")
+        if self.D > N.GPX_MAX_DIM:
+            raise NotImplementedError(f"input dimension {self.D} > {N.GPX_MAX_DIM}")
+        self.M = int(M)
+        self.spec = spec
+        torch.cuda.synchronize(self.device)
+        h = ctypes.c_void_p()
+        rc = self.lib.gpx_sgpr_create(self.ctx.handle, self.N, self.M, self.D,
+                                      ctypes.c_void_p(self.X.data_ptr()), ctypes.c_void_p(self.Y.data_ptr()),
+                                      ctypes.byref(self.spec), ctypes.byref(h))
+        if rc != N.GPX_OK:
+            raise N.GPXError(f"gpx_sgpr_create failed ({rc}): {self.ctx.last_error()}")
+        self.handle = h
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h is not None and h.value:
+            try:
+                self.lib.gpx_sgpr_destroy(h)
+            except Exception:
+                pass
+            self.handle = None
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _args(self, theta, Z):
+        host = SVGPEngine._host
+        self._keep = (host(theta, (N.GPX_THETA_STRIDE,)), host(Z, (self.M, self.D)))
+        dp = ctypes.POINTER(ctypes.c_double)
+        return [a.ctypes.data_as(dp) for a in self._keep]
+
+    def _raise(self, rc, what, info):
+        if rc == N.GPX_NOT_PD:
+            which, pivot = ("Kuu + jitter I", int(info[0])) if info[0] != 0 else ("B = I + A Aᵀ", int(info[1]))
+            raise N.NotPositiveDefiniteError(
+                f"Cholesky decomposition was not successful (pivot {pivot}): {which} is not positive definite",
+                pivot)
+        if rc != N.GPX_OK:
+            raise N.GPXError(f"{what} failed ({rc}): {self.ctx.last_error()}")
+
+    def elbo_grad(self, theta, Z):
+        """The collapsed bound F and ∂F/∂(θ, Z) in constrained space."""
+        elbo = np.zeros(1)
+        gth = np.zeros(N.GPX_THETA_STRIDE)
+        gZ = np.zeros((self.M, self.D))
+        info = (ctypes.c_int32 * 2)(0, 0)
+        dp = ctypes.POINTER(ctypes.c_double)
+        rc = self.lib.gpx_sgpr_elbo_grad(self.handle, *self._args(theta, Z), elbo.ctypes.data_as(dp),
+                                         gth.ctypes.data_as(dp), gZ.ctypes.data_as(dp), info, self._stream())
+        self._raise(rc, "gpx_sgpr_elbo_grad", info)
+        return float(elbo[0]), gth, gZ
+
+    def predict(self, theta, Z, Xnew, add_noise: bool):
+        x = _rows(to_device_f64(Xnew, self.device), self.D).contiguous()
+        if x.shape[1] != self.D:
+            raise ValueError(f"Xnew must have {self.D} columns")
+        Mn = x.shape[0]
+        mean = torch.empty(Mn, dtype=torch.float64, device=x.device)
+        var = torch.empty(Mn, dtype=torch.float64, device=x.device)
+        if Mn == 0:  # empty Xnew: empty outputs (GPflow returns [0, 1] tensors)
+            return mean, var
+        info = (ctypes.c_int32 * 2)(0, 0)
+        rc = self.lib.gpx_sgpr_predict(self.handle, *self._args(theta, Z), ctypes.c_void_p(x.data_ptr()), Mn,
+                                       1 if add_noise else 0, ctypes.c_void_p(mean.data_ptr()),
+                                       ctypes.c_void_p(var.data_ptr()), info, self._stream())
+        self._raise(rc, "gpx_sgpr_predict", info)
+        return mean, var
+
+
 # ----------------------------------------------------------------------------------------
 # pooled single-problem engines for models used on their own (no batch engine attached)
 # ----------------------------------------------------------------------------------------

@@ -437,3 +437,160 @@ class SVGP:
         if cpu_out:
             m, v = m.cpu(), v.cpu()
         return m, v
+
+
+class SGPR:
+    """gpflow.models.SGPR: sparse GP regression by the collapsed (Titsias) bound, Gaussian
+    likelihood, zero mean, one output — the cell at test_scripts/SVGP.py:395-412::
+
+        m = SGPR((X, Y), kernel=SquaredExponential(), inducing_variable=np.linspace(0, 360, 10)[:, None])
+        Scipy().minimize(m.training_loss, m.trainable_variables)
+        mean, var = m.predict_y(X_test)
+
+    The bound, its gradients and the predictions come from libgpx.so (gpx_sgpr_*); trainable
+    variables are ordered as tf.Module flattens SGPR: inducing_variable.Z, kernel.*,
+    likelihood.variance. Not provided: mean functions, several output columns, other
+    likelihoods, full_cov, upper_bound."""
+
+    def __init__(self, data: Tuple, kernel: Kernel, inducing_variable, *, mean_function=None,
+                 num_latent_gps: Optional[int] = None, noise_variance: Optional[float] = None,
+                 likelihood: Optional[Gaussian] = None, device: Optional[int] = None):
+        from .inducing_variables import InducingPoints
+        if mean_function is not None and not isinstance(mean_function, Zero):
+            raise NotImplementedError("SGPR supports only the zero mean function (GPflow's default)")
+        if num_latent_gps not in (None, 1):
+            raise NotImplementedError("SGPR supports one latent GP (Y must be [N, 1])")
+        X, Y = data
+        self._out_cpu = not (isinstance(Y, torch.Tensor) and Y.is_cuda)
+        Xt = X if isinstance(X, torch.Tensor) else torch.as_tensor(np.asarray(X, dtype=np.float64))
+        Yt = Y if isinstance(Y, torch.Tensor) else torch.as_tensor(np.asarray(Y, dtype=np.float64))
+        Xt, Yt = Xt.to(torch.float64), Yt.to(torch.float64)
+        if Xt.ndim == 1:
+            Xt = Xt[:, None]
+        if Yt.ndim == 1:
+            Yt = Yt[:, None]
+        if Yt.shape[1] != 1:
+            raise NotImplementedError("single-output SGPR only (Y must be [N, 1])")
+        if Xt.shape[0] != Yt.shape[0]:
+            raise ValueError("X and Y must have the same number of rows")
+        if Xt.shape[0] == 0:
+            raise ValueError("SGPR needs at least one training point (X has 0 rows)")
+        if likelihood is None:
+            likelihood = Gaussian(1.0 if noise_variance is None else noise_variance)
+        elif noise_variance is not None:
+            raise ValueError("give either noise_variance or likelihood")
+        if not isinstance(likelihood, Gaussian):
+            raise NotImplementedError("SGPR supports the Gaussian likelihood")
+        self.data = (Xt, Yt)
+        self.kernel = kernel
+        self.likelihood = likelihood
+        self.mean_function = mean_function
+        self.inducing_variable = (inducing_variable if isinstance(inducing_variable, InducingPoints)
+                                  else InducingPoints(inducing_variable))
+        if self.inducing_variable.Z.shape[1] != Xt.shape[1]:
+            raise ValueError("inducing points and X must have the same number of columns")
+        self.num_latent_gps = 1
+        self.device = default_device() if device is None else int(device)
+        self._spec = compile_spec(kernel, Xt.shape[1])
+        self._engine = None
+
+    # ---------------------------------------------------------------- structure -------
+    @property
+    def parameters(self):
+        return ((self.inducing_variable.Z,) + tuple(self.kernel.parameters) + tuple(self.likelihood.parameters))
+
+    @property
+    def trainable_parameters(self):
+        return tuple(p for p in self.parameters if p.trainable)
+
+    @property
+    def trainable_variables(self):
+        return tuple(p.unconstrained_variable for p in self.trainable_parameters)
+
+    def _param_paths(self):
+        return ([("SGPR.inducing_variable.Z", self.inducing_variable.Z)]
+                + [("SGPR.kernel." + n if n else "SGPR.kernel", p) for n, p in self.kernel._param_paths("")]
+                + [("SGPR.likelihood.variance", self.likelihood.variance)])
+
+    @property
+    def M(self) -> int:
+        return self.inducing_variable.num_inducing
+
+    def theta_row(self) -> np.ndarray:
+        row = np.ones(N.GPX_THETA_STRIDE, dtype=np.float64)
+        kp = self.kernel.parameters
+        for i, p in enumerate(kp):
+            row[i] = p.value
+        row[len(kp)] = self.likelihood.variance.value
+        return row
+
+    def _state(self):
+        return self.theta_row(), self.inducing_variable.Z.value
+
+    # ---------------------------------------------------------------- engine ----------
+    def engine(self) -> "SGPREngine":
+        from .engine import SGPREngine
+        if self._engine is None:
+            self._engine = SGPREngine(self.data[0], self.data[1], self._spec, self.M, device=self.device)
+        return self._engine
+
+    # ---------------------------------------------------------------- objective -------
+    def _elbo_and_grads(self):
+        return self.engine().elbo_grad(*self._state())
+
+    def elbo(self) -> torch.Tensor:
+        return torch.tensor(self._elbo_and_grads()[0], dtype=torch.float64)
+
+    def maximum_log_likelihood_objective(self) -> torch.Tensor:
+        return self.elbo()
+
+    def training_loss(self) -> torch.Tensor:
+        """−F (no priors), the bound method the reference hands to Scipy().minimize."""
+        return -self.elbo()
+
+    def training_loss_closure(self, compile: bool = True):
+        def closure():
+            return self.training_loss()
+        closure._gpx_model = self
+        return closure
+
+    def grads_to_unconstrained(self, variables, elbo, gth, gZ):
+        """(−F, ∂(−F)/∂u flattened in ``variables`` order)."""
+        kp = self.kernel.parameters
+        pindex = {id(p): i for i, p in enumerate(kp)}
+        parts = []
+        for v in variables:
+            p = v._param
+            if p is self.inducing_variable.Z:
+                parts.append(-np.asarray(gZ).ravel())
+            elif p is self.likelihood.variance:
+                parts.append(np.array([-gth[len(kp)] * p.dtheta_du()]))
+            elif id(p) in pindex:
+                parts.append(np.array([-gth[pindex[id(p)]] * p.dtheta_du()]))
+            else:
+                raise ValueError(f"variable {v.name} is not a parameter of this model")
+        return -float(elbo), np.concatenate(parts)
+
+    def loss_and_grad_unconstrained(self, variables=None):
+        variables = self.trainable_variables if variables is None else variables
+        return self.grads_to_unconstrained(variables, *self._elbo_and_grads())
+
+    # ---------------------------------------------------------------- prediction ------
+    def predict_f(self, Xnew, full_cov: bool = False, full_output_cov: bool = False):
+        if full_cov or full_output_cov:
+            raise NotImplementedError("SGPR.predict_f supports full_cov=False (marginals)")
+        return self._predict(Xnew, False)
+
+    def predict_y(self, Xnew, full_cov: bool = False, full_output_cov: bool = False):
+        if full_cov or full_output_cov:
+            raise NotImplementedError("The predict_y method currently supports only the argument "
+                                      "values full_cov=False and full_output_cov=False")
+        return self._predict(Xnew, True)
+
+    def _predict(self, Xnew, add_noise: bool):
+        cpu_out = not (isinstance(Xnew, torch.Tensor) and Xnew.is_cuda)
+        m, v = self.engine().predict(*self._state(), Xnew, add_noise)
+        m, v = m.reshape(-1, 1), v.reshape(-1, 1)
+        if cpu_out:
+            m, v = m.cpu(), v.cpu()
+        return m, v
