@@ -433,9 +433,9 @@ int gpx_svgp_predict(gpx_svgp* svgp, const double* theta, const double* Z, const
  * Two M x M factorisations run per call, so info points to TWO int32: info[0] the first failing
  * pivot (1-based, 0 = ok) of Kmm = k(Z,Z) + 1e-6 I, info[1] that of B = I + L⁻¹ Kmn Kmnᵀ L⁻ᵀ/σn²
  * (I + PSD: a failure there means a non-finite input). Either one returns GPX_NOT_PD.
- * Not provided: mean functions, multi-output Y, full_cov, upper_bound, other likelihoods (VGP /
- * StudentT), and row-sharding over GPUs — K̄mn depends on the all-reduced B, so shards would need
- * a two-pass protocol that gpx_svgp_partials does not give.
+ * Not provided: mean functions, multi-output Y, full_cov, upper_bound, other likelihoods (those
+ * are gpx_vgp's), and row-sharding over GPUs — K̄mn depends on the all-reduced B, so shards would
+ * need a two-pass protocol that gpx_svgp_partials does not give.
  */
 typedef struct gpx_sgpr gpx_sgpr;
 int gpx_sgpr_create(gpx_ctx* ctx, int N, int M, int D, const double* X, const double* Y,
@@ -446,6 +446,40 @@ int gpx_sgpr_elbo_grad(gpx_sgpr* sgpr, const double* theta, const double* Z, dou
 /* predict_f (add_noise = 0) / predict_y (1) at Xnew (device [Mn, D]) -> mean, var (device [Mn]) */
 int gpx_sgpr_predict(gpx_sgpr* sgpr, const double* theta, const double* Z, const double* Xnew, int Mn,
                      int add_noise, double* mean, double* var, int32_t* info, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * VGP: gpflow.models.VGP((X, Y), kernel, likelihood) with GPflow's defaults — whitened
+ * q(f) = N(L q_mu, L q_sqrt q_sqrtᵀ Lᵀ), L = chol(k(X,X) + 1e-6 I), full q_sqrt, zero mean, one
+ * output; test_scripts/SVGP.py:402-437 (SE kernel, StudentT likelihood, N ≈ 113).
+ *   gpx_vgp_elbo_grad  <- model.training_loss value + gradient, fed to
+ *                         gpflow.optimizers.Scipy().minimize(model.training_loss, ...)
+ *   gpx_vgp_predict    <- model.predict_f(X_test) (predict_y = 0) / model.predict_y (1)
+ * likelihood: GPX_LIK_GAUSSIAN (closed-form variational expectation) or GPX_LIK_STUDENT_T
+ * (GPflow's 20-point Gauss–Hermite rule; df is fixed at create and must be > 0, predict_y
+ * needs df > 2).
+ * X [N, D] and Y [N] are device-resident fp64 and caller-owned; they must outlive the object.
+ * Per evaluation (host): theta [16] = kernel params (gpx_kernel_spec layout) then the likelihood
+ * parameter at theta[n_params] (Gaussian variance / StudentT scale); q_mu [N]; q_sqrt [N][N]
+ * row-major, its lower triangle is read. Outputs (host): elbo; grad_theta [16] (constrained,
+ * likelihood parameter at n_params); grad_qmu [N]; grad_qsqrt [N][N] (lower, zeros above).
+ * X is data: no input gradient. info: first failing pivot (1-based, 0 = ok) of k(X,X) + 1e-6 I
+ * (GPX_NOT_PD). theta not finite or <= 0, non-finite q_mu / q_sqrt and a zero diagonal of q_sqrt
+ * return GPX_BAD_ARG. The workspace is thirteen N x N fp64 matrices.
+ * predict: Xnew device [Mn, D] -> mean, var device [Mn]; predict_y adds the likelihood's
+ * variance (σn², or scale²·df/(df − 2)).
+ * Not provided: mean functions, multi-output Y, full_cov, sharding, several VGPs per call.
+ */
+enum { GPX_LIK_GAUSSIAN = 0, GPX_LIK_STUDENT_T = 1 };
+typedef struct gpx_vgp gpx_vgp;
+int gpx_vgp_create(gpx_ctx* ctx, int N, int D, const double* X, const double* Y,
+                   const gpx_kernel_spec* spec, int likelihood, double df, gpx_vgp** out);
+int gpx_vgp_destroy(gpx_vgp* vgp);
+int gpx_vgp_elbo_grad(gpx_vgp* vgp, const double* theta, const double* q_mu, const double* q_sqrt,
+                      double* elbo, double* grad_theta, double* grad_qmu, double* grad_qsqrt,
+                      int32_t* info, void* stream);
+int gpx_vgp_predict(gpx_vgp* vgp, const double* theta, const double* q_mu, const double* q_sqrt,
+                    const double* Xnew, int Mn, int predict_y, double* mean, double* var,
+                    int32_t* info, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Host helpers of the batched L-BFGS-B driver (no device work): for the n_fits fits of one

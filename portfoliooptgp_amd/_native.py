@@ -20,6 +20,7 @@ GPX_MAX_DIM = 16
  GPX_LINEAR) = range(1, 9)
 GPX_SUM, GPX_PRODUCT = 0, 1
 # gpx_mean_kind (include/gpx.h)
+GPX_LIK_GAUSSIAN, GPX_LIK_STUDENT_T = 0, 1
 GPX_MEAN_ZERO, GPX_MEAN_CONSTANT, GPX_MEAN_LINEAR, GPX_MEAN_POLYNOMIAL = range(4)
 # per-variable transform codes of gpx_host_theta_rows_t / gpx_host_loss_grad_u_t
 TRANSFORM_SOFTPLUS, TRANSFORM_IDENTITY = 0, 1
@@ -45,6 +46,7 @@ EXPORTED_SYMBOLS = (
     "gpx_svgp_create", "gpx_svgp_destroy", "gpx_svgp_partials", "gpx_svgp_bind_partials",
     "gpx_svgp_eval_local", "gpx_svgp_eval_finish", "gpx_svgp_elbo_grad", "gpx_svgp_predict",
     "gpx_sgpr_create", "gpx_sgpr_destroy", "gpx_sgpr_elbo_grad", "gpx_sgpr_predict",
+    "gpx_vgp_create", "gpx_vgp_destroy", "gpx_vgp_elbo_grad", "gpx_vgp_predict",
     "gpx_host_theta_rows", "gpx_host_loss_grad_u",
     "gpx_batch_set_mean", "gpx_host_theta_rows_t", "gpx_host_loss_grad_u_t",
 )
@@ -236,6 +238,17 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.gpx_sgpr_predict.restype = c_int
         lib.gpx_sgpr_predict.argtypes = [c_void_p, c_double_p, c_double_p, c_void_p, c_int, c_int,
                                          c_void_p, c_void_p, c_int_p, c_void_p]
+        lib.gpx_vgp_create.restype = c_int
+        lib.gpx_vgp_create.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, spec_p, c_int, c_double,
+                                       ctypes.POINTER(c_void_p)]
+        lib.gpx_vgp_destroy.restype = c_int
+        lib.gpx_vgp_destroy.argtypes = [c_void_p]
+        lib.gpx_vgp_elbo_grad.restype = c_int
+        lib.gpx_vgp_elbo_grad.argtypes = [c_void_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                          c_double_p, c_double_p, c_double_p, c_int_p, c_void_p]
+        lib.gpx_vgp_predict.restype = c_int
+        lib.gpx_vgp_predict.argtypes = [c_void_p, c_double_p, c_double_p, c_double_p, c_void_p, c_int, c_int,
+                                        c_void_p, c_void_p, c_int_p, c_void_p]
         lib.gpx_host_theta_rows.restype = c_int
         lib.gpx_host_theta_rows.argtypes = [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
         lib.gpx_host_loss_grad_u.restype = c_int

@@ -1,6 +1,6 @@
 // gpx_host.h — host-side internals shared by the exact-GP host files (gpx_api.hip: lifetime,
 // rebinds, setters; gpx_dense.hip; gpx_route.hip; gpx_eval.hip; gpx_predict.hip) and the SVGP /
-// SGPR orchestration (gpx_svgp.hip, gpx_sgpr.hip): context / batch state, error plumbing and the device building
+// SGPR / VGP orchestration (gpx_svgp.hip, gpx_sgpr.hip, gpx_vgp.hip): context / batch state, error plumbing and the device building
 // blocks (K build + recursive Cholesky-and-inverse, batched MFMA GEMM).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -400,4 +400,39 @@ void launch_sgpr_final(const SgprFinalArgs& a, hipStream_t s);
 int sgpr_final_blocks(int m);
 void launch_vscale(const double* x, double* y, int n, double c, hipStream_t s);  // y = c x
 
+// ---- VGP (gpx_vgp.hip; kernels in gpx_vgp_kernels.hip) ---------------------------------
+constexpr int kGhPoints = 20;  // GPflow's default Gauss–Hermite rule (NDiagGHQuadrature)
+// L from P = K̃ Wᵀ in place: zeros above the diagonal, the identity on rows / columns >= n
+struct VgpLtriArgs {
+  double* L; int n; int np;
+};
+// one wave per row of the lower-triangular A [rows][ld], entries j <= row:
+//   gv == nullptr: v[row] = Σ_j A², else GA[row][j] = gv[row] A[row][j]
+struct VgpRowsqArgs {
+  const double* A; int ld; int rows;
+  const double* gv;
+  double* v; double* GA;
+};
+// the variational expectations, one row per lane; block partials [vgp_quad_blocks(npad)][2]:
+// Σ ve, Σ ∂ve/∂φ with φ the likelihood parameter (Gaussian variance / Student-t scale)
+struct VgpQuadArgs {
+  const double* mu; const double* v; const double* y; int n; int npad;
+  int lik; double phi; double df; double c0;
+  double* gmu; double* gv;   // [npad], zero beyond n
+  double* part;
+};
+// N×N tail: Phi = Φ(t qᵀ + 2 C Rᵀ) [ld], Rbar = tril(2C − R + diag(1/R_ii)) [n][n] compact,
+// info_out[0] = (double)info[0]
+struct VgpFinalArgs {
+  const double* C; const double* CRt; const double* t; const double* q; const double* R;
+  int n, ld;
+  double* Phi; double* Rbar;
+  const int* info; double* info_out;
+};
+void launch_vgp_ltri(const VgpLtriArgs& a, hipStream_t s);
+void launch_vgp_rowsq(const VgpRowsqArgs& a, hipStream_t s);
+void launch_vgp_quad(const VgpQuadArgs& a, hipStream_t s);
+int vgp_quad_blocks(int npad);
+void launch_vgp_final(const VgpFinalArgs& a, hipStream_t s);
+
 }  // namespace gpx

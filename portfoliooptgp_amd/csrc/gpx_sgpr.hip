@@ -19,8 +19,8 @@
 // Y = (WᵀHW) Kmn and the rows contraction, plus two O(MN)/O(N) streams (w, the k_nn pass). B is
 // factored by the same recursive Cholesky-and-inverse as Kmm, in a second B = 1 batch.
 //
-// Out of scope: mean functions, multi-output Y, full_cov, upper_bound, VGP / StudentT, and
-// row-sharding over GPUs (K̄mn depends on the all-reduced B, so shards would need two passes —
+// Out of scope: mean functions, multi-output Y, full_cov, upper_bound, other likelihoods (those are
+// gpx_vgp.hip's), and row-sharding over GPUs (K̄mn depends on the all-reduced B, so shards would need two passes —
 // one for G and w, one for the contraction — which the gpx_svgp_partials protocol does not give).
 #include <hip/hip_runtime.h>
 #include <algorithm>

@@ -829,6 +829,94 @@ class SGPREngine:
         return mean, var
 
 
+class VGPEngine:
+    """Device state of one VGP model (include/gpx.h gpx_vgp): X [N, D] / Y [N] resident in HBM,
+    the N x N factorisation and GEMM workspace owned by the library. ``likelihood`` is
+    N.GPX_LIK_GAUSSIAN or N.GPX_LIK_STUDENT_T (with its fixed ``df``)."""
+
+    def __init__(self, X, Y, spec: N.GpxKernelSpec, likelihood: int, df: float = 3.0,
+                 device: Optional[int] = None):
+        self.device = require_gpu(device)
+        self.ctx = N.Context.get(self.device)
+        self.lib = self.ctx.lib
+        x = to_device_f64(X, self.device)
+        self.X = x.reshape(x.shape[0], -1).contiguous()
+        self.Y = to_device_f64(Y, self.device).reshape(-1).contiguous()
+        self.N, self.D = self.X.shape
+        if self.Y.shape[0] != self.N:
+            raise ValueError("X and Y must have the same number of rows")
+        if self.D > N.GPX_MAX_DIM:
+            raise NotImplementedError(f"input dimension {self.D} > {N.GPX_MAX_DIM}")
+        self.spec = spec
+        torch.cuda.synchronize(self.device)
+        h = ctypes.c_void_p()
+        rc = self.lib.gpx_vgp_create(self.ctx.handle, self.N, self.D, ctypes.c_void_p(self.X.data_ptr()),
+                                     ctypes.c_void_p(self.Y.data_ptr()), ctypes.byref(self.spec),
+                                     int(likelihood), float(df), ctypes.byref(h))
+        if rc != N.GPX_OK:
+            raise N.GPXError(f"gpx_vgp_create failed ({rc}): {self.ctx.last_error()}")
+        self.handle = h
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h is not None and h.value:
+            try:
+                self.lib.gpx_vgp_destroy(h)
+            except Exception:
+                pass
+            self.handle = None
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _args(self, theta, q_mu, q_sqrt):
+        host = SVGPEngine._host
+        self._keep = (host(theta, (N.GPX_THETA_STRIDE,)), host(q_mu, (self.N,)), host(q_sqrt, (self.N, self.N)))
+        dp = ctypes.POINTER(ctypes.c_double)
+        return [a.ctypes.data_as(dp) for a in self._keep]
+
+    def _raise(self, rc, what, info):
+        if rc == N.GPX_NOT_PD:
+            raise N.NotPositiveDefiniteError(
+                f"Cholesky decomposition was not successful (pivot {int(info.value)}): "
+                "K(X, X) + jitter I is not positive definite", int(info.value))
+        if rc != N.GPX_OK:
+            raise N.GPXError(f"{what} failed ({rc}): {self.ctx.last_error()}")
+
+    def elbo_grad(self, theta, q_mu, q_sqrt):
+        """ELBO and ∂ELBO/∂(θ, q_mu, q_sqrt) in constrained space; θ[n_params] is the likelihood
+        parameter (Gaussian variance / StudentT scale)."""
+        n = self.N
+        elbo = np.zeros(1)
+        gth = np.zeros(N.GPX_THETA_STRIDE)
+        gq = np.zeros(n)
+        gR = np.zeros((n, n))
+        info = ctypes.c_int32(0)
+        dp = ctypes.POINTER(ctypes.c_double)
+        rc = self.lib.gpx_vgp_elbo_grad(self.handle, *self._args(theta, q_mu, q_sqrt), elbo.ctypes.data_as(dp),
+                                        gth.ctypes.data_as(dp), gq.ctypes.data_as(dp), gR.ctypes.data_as(dp),
+                                        ctypes.byref(info), self._stream())
+        self._raise(rc, "gpx_vgp_elbo_grad", info)
+        return float(elbo[0]), gth, gq, gR
+
+    def predict(self, theta, q_mu, q_sqrt, Xnew, predict_y: bool):
+        x = _rows(to_device_f64(Xnew, self.device), self.D).contiguous()
+        if x.shape[1] != self.D:
+            raise ValueError(f"Xnew must have {self.D} columns")
+        Mn = x.shape[0]
+        mean = torch.empty(Mn, dtype=torch.float64, device=x.device)
+        var = torch.empty(Mn, dtype=torch.float64, device=x.device)
+        if Mn == 0:  # empty Xnew: empty outputs (GPflow returns [0, 1] tensors)
+            return mean, var
+        info = ctypes.c_int32(0)
+        rc = self.lib.gpx_vgp_predict(self.handle, *self._args(theta, q_mu, q_sqrt),
+                                      ctypes.c_void_p(x.data_ptr()), Mn, 1 if predict_y else 0,
+                                      ctypes.c_void_p(mean.data_ptr()), ctypes.c_void_p(var.data_ptr()),
+                                      ctypes.byref(info), self._stream())
+        self._raise(rc, "gpx_vgp_predict", info)
+        return mean, var
+
+
 # ----------------------------------------------------------------------------------------
 # pooled single-problem engines for models used on their own (no batch engine attached)
 # ----------------------------------------------------------------------------------------

@@ -22,7 +22,7 @@ import torch
 from . import _native as N
 from .engine import Engine, default_device, solo_engine
 from .kernels import Kernel, compile_spec
-from .likelihoods import Gaussian
+from .likelihoods import Gaussian, StudentT
 from .mean_functions import MeanFunction, Zero
 from .parameter import ArrayParameter, Parameter
 
@@ -590,6 +590,166 @@ class SGPR:
     def _predict(self, Xnew, add_noise: bool):
         cpu_out = not (isinstance(Xnew, torch.Tensor) and Xnew.is_cuda)
         m, v = self.engine().predict(*self._state(), Xnew, add_noise)
+        m, v = m.reshape(-1, 1), v.reshape(-1, 1)
+        if cpu_out:
+            m, v = m.cpu(), v.cpu()
+        return m, v
+
+
+class VGP:
+    """gpflow.models.VGP with GPflow's defaults (whitened, full q_sqrt, zero mean, one latent GP)
+    and a Gaussian or StudentT likelihood — the cell at test_scripts/SVGP.py:402-437::
+
+        m = VGP((X, Y), kernel=SquaredExponential(), likelihood=StudentT())
+        Scipy().minimize(m.training_loss, m.trainable_variables)
+        mean, var = m.predict_y(X_test)
+
+    q_mu starts at zeros [N, 1], q_sqrt at the identity [1, N, N]. The ELBO (closed form for the
+    Gaussian, GPflow's 20-point Gauss–Hermite rule for StudentT), its gradients and the predictions
+    come from libgpx.so (gpx_vgp_*); trainable variables are ordered as tf.Module flattens VGP:
+    kernel.*, likelihood.scale / likelihood.variance, q_mu, q_sqrt (FillTriangular-unconstrained).
+    Not provided: mean functions, several output columns, other likelihoods, full_cov."""
+
+    def __init__(self, data: Tuple, kernel: Kernel, likelihood, mean_function=None,
+                 num_latent_gps: Optional[int] = None, device: Optional[int] = None):
+        if mean_function is not None and not isinstance(mean_function, Zero):
+            raise NotImplementedError("VGP supports only the zero mean function (GPflow's default)")
+        if num_latent_gps not in (None, 1):
+            raise NotImplementedError("VGP supports one latent GP (Y must be [N, 1])")
+        if not isinstance(likelihood, (Gaussian, StudentT)):
+            raise NotImplementedError("VGP supports the Gaussian and StudentT likelihoods")
+        X, Y = data
+        Xt = X if isinstance(X, torch.Tensor) else torch.as_tensor(np.asarray(X, dtype=np.float64))
+        Yt = Y if isinstance(Y, torch.Tensor) else torch.as_tensor(np.asarray(Y, dtype=np.float64))
+        Xt, Yt = Xt.to(torch.float64), Yt.to(torch.float64)
+        if Xt.ndim == 1:
+            Xt = Xt[:, None]
+        if Yt.ndim == 1:
+            Yt = Yt[:, None]
+        if Yt.shape[1] != 1:
+            raise NotImplementedError("single-output VGP only (Y must be [N, 1])")
+        if Xt.shape[0] != Yt.shape[0]:
+            raise ValueError("X and Y must have the same number of rows")
+        if Xt.shape[0] == 0:
+            raise ValueError("VGP needs at least one training point (X has 0 rows)")
+        n = int(Xt.shape[0])
+        self.data = (Xt, Yt)
+        self.kernel = kernel
+        self.likelihood = likelihood
+        self.mean_function = mean_function
+        self.num_data = n
+        self.num_latent_gps = 1
+        self.q_mu = ArrayParameter(np.zeros((n, 1)), name="q_mu")
+        self.q_sqrt = ArrayParameter(np.eye(n)[None], transform="triangular", name="q_sqrt")
+        self.device = default_device() if device is None else int(device)
+        self._spec = compile_spec(kernel, Xt.shape[1])
+        self._engine = None
+
+    # ---------------------------------------------------------------- structure -------
+    @property
+    def _lik_param(self) -> Parameter:
+        return self.likelihood.scale if isinstance(self.likelihood, StudentT) else self.likelihood.variance
+
+    @property
+    def parameters(self):
+        return tuple(self.kernel.parameters) + tuple(self.likelihood.parameters) + (self.q_mu, self.q_sqrt)
+
+    @property
+    def trainable_parameters(self):
+        return tuple(p for p in self.parameters if p.trainable)
+
+    @property
+    def trainable_variables(self):
+        return tuple(p.unconstrained_variable for p in self.trainable_parameters)
+
+    def _param_paths(self):
+        return ([("VGP.kernel." + n if n else "VGP.kernel", p) for n, p in self.kernel._param_paths("")]
+                + [("VGP.likelihood." + self._lik_param.name, self._lik_param),
+                   ("VGP.q_mu", self.q_mu), ("VGP.q_sqrt", self.q_sqrt)])
+
+    def theta_row(self) -> np.ndarray:
+        row = np.ones(N.GPX_THETA_STRIDE, dtype=np.float64)
+        kp = self.kernel.parameters
+        for i, p in enumerate(kp):
+            row[i] = p.value
+        row[len(kp)] = self._lik_param.value
+        return row
+
+    def _state(self):
+        return self.theta_row(), self.q_mu.value.reshape(-1), self.q_sqrt.value[0]
+
+    # ---------------------------------------------------------------- engine ----------
+    def engine(self) -> "VGPEngine":
+        from .engine import VGPEngine
+        if self._engine is None:
+            st = isinstance(self.likelihood, StudentT)
+            self._engine = VGPEngine(self.data[0], self.data[1], self._spec,
+                                     N.GPX_LIK_STUDENT_T if st else N.GPX_LIK_GAUSSIAN,
+                                     df=self.likelihood.df if st else 3.0, device=self.device)
+        return self._engine
+
+    # ---------------------------------------------------------------- objective -------
+    def _elbo_and_grads(self):
+        row = self.theta_row()
+        np_ = len(self.kernel.parameters)
+        if not np.all(np.isfinite(row[:np_ + 1])) or not np.all(row[:np_ + 1] > 0.0):
+            raise N.InvalidParameterError(f"hyperparameters out of (0, inf): {row[:np_ + 1]}")
+        return self.engine().elbo_grad(*self._state())
+
+    def elbo(self) -> torch.Tensor:
+        return torch.tensor(self._elbo_and_grads()[0], dtype=torch.float64)
+
+    def maximum_log_likelihood_objective(self) -> torch.Tensor:
+        return self.elbo()
+
+    def training_loss(self) -> torch.Tensor:
+        """−ELBO (no priors), the bound method the reference hands to Scipy().minimize."""
+        return -self.elbo()
+
+    def training_loss_closure(self, compile: bool = True):
+        def closure():
+            return self.training_loss()
+        closure._gpx_model = self
+        return closure
+
+    def grads_to_unconstrained(self, variables, elbo, gth, gq, gR):
+        """(−ELBO, ∂(−ELBO)/∂u flattened in ``variables`` order)."""
+        kp = self.kernel.parameters
+        pindex = {id(p): i for i, p in enumerate(kp)}
+        parts = []
+        for v in variables:
+            p = v._param
+            if p is self._lik_param:
+                parts.append(np.array([-gth[len(kp)] * p.dtheta_du()]))
+            elif id(p) in pindex:
+                parts.append(np.array([-gth[pindex[id(p)]] * p.dtheta_du()]))
+            elif p is self.q_mu:
+                parts.append(-np.asarray(gq).ravel())
+            elif p is self.q_sqrt:
+                parts.append(-p.grad_to_unconstrained(gR).ravel())
+            else:
+                raise ValueError(f"variable {v.name} is not a parameter of this model")
+        return -float(elbo), np.concatenate(parts)
+
+    def loss_and_grad_unconstrained(self, variables=None):
+        variables = self.trainable_variables if variables is None else variables
+        return self.grads_to_unconstrained(variables, *self._elbo_and_grads())
+
+    # ---------------------------------------------------------------- prediction ------
+    def predict_f(self, Xnew, full_cov: bool = False, full_output_cov: bool = False):
+        if full_cov or full_output_cov:
+            raise NotImplementedError("VGP.predict_f supports full_cov=False (marginals)")
+        return self._predict(Xnew, False)
+
+    def predict_y(self, Xnew, full_cov: bool = False, full_output_cov: bool = False):
+        if full_cov or full_output_cov:
+            raise NotImplementedError("The predict_y method currently supports only the argument "
+                                      "values full_cov=False and full_output_cov=False")
+        return self._predict(Xnew, True)
+
+    def _predict(self, Xnew, predict_y: bool):
+        cpu_out = not (isinstance(Xnew, torch.Tensor) and Xnew.is_cuda)
+        m, v = self.engine().predict(*self._state(), Xnew, predict_y)
         m, v = m.reshape(-1, 1), v.reshape(-1, 1)
         if cpu_out:
             m, v = m.cpu(), v.cpu()
