@@ -40,6 +40,11 @@
  *      RationalQuadratic                         : [alpha, lengthscales, variance]
  *      Periodic(SquaredExponential)              : [base.lengthscales, base.variance, period]
  *      Linear                                    : [variance]
+ *    With GPX_TERM_ARD in a stationary term's kind (one lengthscale per active dimension, GPflow's
+ *    vector `lengthscales`; see gpx_term below) its dim_count lengthscales take the scalar's place:
+ *      SE/Matern/Exponential | GPX_TERM_ARD      : [l_0 .. l_{dim_count-1}, variance]
+ *      RationalQuadratic | GPX_TERM_ARD          : [alpha, l_0 .. l_{dim_count-1}, variance]
+ *    Such problems always take the dense path, in the same batches and calls as the others.
  *  - Return codes: GPX_OK, GPX_NOT_PD (some problem's K+σn²I is not positive definite; its
  *    info[b] holds the 1-based index of the first failing pivot, like LAPACK potrf),
  *    GPX_BAD_ARG, GPX_HIP_ERROR. No C++ exception crosses this boundary.
@@ -84,8 +89,25 @@ typedef enum {
 
 typedef enum { GPX_SUM = 0, GPX_PRODUCT = 1 } gpx_combine;
 
+/*
+ * ARD (one lengthscale per active dimension, GPflow's vector `lengthscales`): OR this flag into
+ * gpx_term.kind. Valid with SE, Matern12/32/52, Exponential and RationalQuadratic and
+ * dim_count >= 2 only (anything else: GPX_BAD_ARG). The term then takes dim_count lengthscale
+ * slots in place of one, flattened where the scalar sits:
+ *      SE/Matern/Exponential | GPX_TERM_ARD : [l_0 .. l_{dim_count-1}, variance]
+ *      RationalQuadratic     | GPX_TERM_ARD : [alpha, l_0 .. l_{dim_count-1}, variance]
+ * with r² formed from x_d / l_d. A spec with an ARD term always takes the dense route (never band
+ * storage's sweeps: gpx_batch_band_width / _band_class report it as dense), its stationary terms
+ * may cover at most GPX_MAX_DIM input columns in total (plus D when a Linear or Periodic term is
+ * present), it leaves the theta row's last column free (n_params + 1 <= GPX_THETA_STRIDE - 1: up to
+ * 13 lengthscales for a single term), and it is accepted by the gpx_batch_* entry points only
+ * (gpx_svgp / gpx_sgpr / gpx_vgp refuse it). grad carries dlogML/dl_d in each l_d's column.
+ */
+#define GPX_TERM_ARD 0x100
+#define GPX_TERM_KIND_MASK 0xff
+
 typedef struct {
-  int32_t kind;         /* gpx_term_kind */
+  int32_t kind;         /* gpx_term_kind, optionally | GPX_TERM_ARD */
   int32_t dim_start;    /* active_dims = slice(dim_start, dim_start + dim_count) */
   int32_t dim_count;
   int32_t param_offset; /* index of this term's first parameter in the theta row */

@@ -18,6 +18,8 @@ GPX_MAX_DIM = 16
 
 (GPX_SE, GPX_MATERN12, GPX_MATERN32, GPX_MATERN52, GPX_EXPONENTIAL, GPX_RQ, GPX_PERIODIC_SE,
  GPX_LINEAR) = range(1, 9)
+# flag bit of gpx_term.kind: ARD, one lengthscale per active dim (include/gpx.h)
+GPX_TERM_ARD, GPX_TERM_KIND_MASK = 0x100, 0xFF
 GPX_SUM, GPX_PRODUCT = 0, 1
 # gpx_mean_kind (include/gpx.h)
 GPX_LIK_GAUSSIAN, GPX_LIK_STUDENT_T = 0, 1

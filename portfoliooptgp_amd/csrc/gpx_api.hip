@@ -156,17 +156,7 @@ static int batch_create(gpx_ctx* ctx, int B, int N_max, int D, const double* X, 
     return fail(ctx, GPX_BAD_ARG, "bad batch dimensions or null pointer");
   for (int b = 0; b < B; ++b) {
     if (n[b] < 1 || n[b] > N_max) return fail(ctx, GPX_BAD_ARG, "n[b] must be in [1, N_max]");
-    const gpx_kernel_spec& sp = specs[b];
-    if (sp.n_terms < 1 || sp.n_terms > GPX_MAX_TERMS || sp.n_params < 1 ||
-        sp.n_params >= GPX_THETA_STRIDE)
-      return fail(ctx, GPX_BAD_ARG, "bad kernel spec");
-    for (int t = 0; t < sp.n_terms; ++t) {
-      const gpx_term& tm = sp.terms[t];
-      const int np = (tm.kind == GPX_RQ || tm.kind == GPX_PERIODIC_SE) ? 3 : (tm.kind == GPX_LINEAR ? 1 : 2);
-      if (tm.kind < GPX_SE || tm.kind > GPX_LINEAR || tm.dim_start < 0 || tm.dim_count < 1 ||
-          tm.dim_start + tm.dim_count > D || tm.param_offset < 0 || tm.param_offset + np > sp.n_params)
-        return fail(ctx, GPX_BAD_ARG, "bad kernel term");
-    }
+    if (const char* why = spec_error(specs[b], D)) return fail(ctx, GPX_BAD_ARG, why);
   }
   if (((long long)N_max + kLeaf - 1) / kLeaf * kLeaf > kGemmMaxLd)
     return fail(ctx, GPX_BAD_ARG, "N_max exceeds the GEMM buffer-load window (kGemmMaxLd)");
@@ -368,16 +358,7 @@ static int check_rebind(gpx_batch* bt, int b, int n, const gpx_kernel_spec* spec
   gpx_ctx* ctx = bt->ctx;
   if (b < 0 || b >= bt->B || n < 1 || n > bt->Nmax || !spec)
     return fail(ctx, GPX_BAD_ARG, "bad rebind arguments");
-  const gpx_kernel_spec& sp = *spec;
-  if (sp.n_terms < 1 || sp.n_terms > GPX_MAX_TERMS || sp.n_params < 1 || sp.n_params >= GPX_THETA_STRIDE)
-    return fail(ctx, GPX_BAD_ARG, "bad kernel spec");
-  for (int t = 0; t < sp.n_terms; ++t) {
-    const gpx_term& tm = sp.terms[t];
-    const int np = (tm.kind == GPX_RQ || tm.kind == GPX_PERIODIC_SE) ? 3 : (tm.kind == GPX_LINEAR ? 1 : 2);
-    if (tm.kind < GPX_SE || tm.kind > GPX_LINEAR || tm.dim_start < 0 || tm.dim_count < 1 ||
-        tm.dim_start + tm.dim_count > bt->D || tm.param_offset < 0 || tm.param_offset + np > sp.n_params)
-      return fail(ctx, GPX_BAD_ARG, "bad kernel term");
-  }
+  if (const char* why = spec_error(*spec, bt->D)) return fail(ctx, GPX_BAD_ARG, why);
   if (!bt->deferred.empty() && b >= 0 && b < bt->B && bt->deferred[b])
     return fail(ctx, GPX_BAD_ARG, "slot has a deferred evaluation in flight (gpx_batch_deferred_wait)");
   return GPX_OK;

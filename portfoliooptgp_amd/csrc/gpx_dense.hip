@@ -129,8 +129,18 @@ void factor(const Run& r) {
   ba.X = bt->X; ba.sX = (long long)bt->Nmax * bt->D; ba.X2 = bt->X; ba.sX2 = ba.sX; ba.D = bt->D;
   ba.m2 = 0; ba.out = bt->K; ba.sOut = mat_stride(bt); ba.ldo = bt->Np; ba.rows = ba.cols = bt->Np;
   ba.symmetric = 1;
-  launch_build(ba, r.na, r.s);
+  build_range(ba, r.na, r.n_ard, r.s);
   chol_inv(r, 0, bt->Np);
+}
+
+// the isotropic problems of a range by build_kernel, its trailing ARD ones by build_ard_kernel
+void build_range(const BuildArgs& a, int na, int n_ard, hipStream_t s) {
+  if (na > n_ard) launch_build(a, na - n_ard, s);
+  if (n_ard > 0) {
+    BuildArgs b = a;
+    b.active = a.active + (na - n_ard);
+    launch_build_ard(b, n_ard, s);
+  }
 }
 
 // z = W y, α = Wᵀ z
@@ -150,6 +160,8 @@ void alpha_solve(const Run& r) {
 }
 
 // fused K⁻¹ = WᵀW formation + gradient contraction over lower tiles, then the reduction
+// (max_terms: over the range's isotropic problems; its ARD ones: r.ard_terms — so an isotropic
+// problem's instance does not depend on the ARD specs that share its call)
 void contract(const Run& r, int max_terms, hipEvent_t ev0, hipEvent_t ev1) {
   gpx_batch* bt = r.bt;
   GemmArgs g = gemm_args(bt->W, bt->Np, bt->W, bt->Np, nullptr, 0, mat_stride(bt), bt->Np, bt->Np,
@@ -158,7 +170,20 @@ void contract(const Run& r, int max_terms, hipEvent_t ev0, hipEvent_t ev1) {
   g.specs = bt->d_specs; g.theta = bt->d_theta; g.nvalid = bt->d_n;
   g.partial = bt->partial; g.sPartial = bt->partial_stride;
   g.ev_start = ev0; g.ev_stop = ev1;
-  gemm(r, g, max_terms <= 1 ? EPI_CONTRACT1 : max_terms == 2 ? EPI_CONTRACT2 : EPI_CONTRACT, true, false);
+  const int n_iso = r.na - r.n_ard;
+  if (n_iso > 0) {
+    Run ri = r;
+    ri.na = n_iso;
+    gemm(ri, g, max_terms <= 1 ? EPI_CONTRACT1 : max_terms == 2 ? EPI_CONTRACT2 : EPI_CONTRACT, true, false);
+    g.ev_start = g.ev_stop = nullptr;  // (a mixed call's contraction time: its isotropic launch)
+  }
+  if (r.n_ard > 0) {
+    // the ARD problems (the range's last n_ard): the θ-indexed epilogue, sized by their own specs
+    Run ra = r;
+    ra.d_act = r.d_act + n_iso;
+    ra.na = r.n_ard;
+    gemm(ra, g, r.ard_terms <= 2 ? EPI_CONTRACT_ARD2 : EPI_CONTRACT_ARD, true, false);
+  }
 }
 
 void reduce(const Run& r) {

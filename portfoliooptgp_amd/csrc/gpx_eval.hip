@@ -1062,8 +1062,9 @@ int submit_all_shadow(SubmitCall& c) {
 bool small_direct_call(const SubmitCall& c) {
   // (not for a batch with a mean function: its gradient kernel follows the fused launch, whose
   // polled flag would tell the host to read the results before that kernel has written its columns)
+  // (nor with ARD problems: they take the launch chain below)
   return knob_on(Knob::SmallDirect) && small64_on(c.bt) && c.rt.n_dense == c.n_active && !c.shadow_async &&
-         c.rt.shadow_ids.empty() && c.bt->n_mean == 0;
+         c.rt.shadow_ids.empty() && c.bt->n_mean == 0 && c.rt.n_ard == 0;
 }
 
 int submit_small_direct(SubmitCall& c) {
@@ -1104,9 +1105,21 @@ int submit_dense(SubmitCall& c, gpx_batch::PendingEval& pe) {
   hipStream_t s = c.s;
   const int n_dense = c.rt.n_dense;
   if (n_dense == 0) return GPX_OK;
+  const int n_ard = c.rt.n_ard, n_iso = n_dense - n_ard;  // (the ARD problems: the last n_ard)
   if (small64_on(bt)) {
     // Np = 64: the whole evaluation of every dense problem in one launch
-    small64_eval(Run{bt, bt->d_active, n_dense, s}, true);
+    if (n_iso > 0) small64_eval(Run{bt, bt->d_active, n_iso, s}, true);
+    if (n_ard > 0) {
+      // an ARD problem of these sizes: the launch chain (build, leaf, solves, contraction, reduce)
+      // with the ARD build and epilogue — by its spec, whatever else the call holds
+      Run ra{bt, bt->d_active + n_iso, n_ard, s};
+      ra.n_ard = n_ard;
+      ra.ard_terms = c.max_terms(n_iso, n_dense);
+      factor(ra);
+      alpha_solve(ra);
+      contract(ra, 1);
+      reduce(ra);
+    }
     return GPX_OK;
   }
   // Split the dense problems into up to kGroups ranges, each running the whole pipeline on
@@ -1128,6 +1141,7 @@ int submit_dense(SubmitCall& c, gpx_batch::PendingEval& pe) {
   for (int g = 0; g < ng; ++g) {
     const int cnt = n_dense / ng + (g < n_dense % ng ? 1 : 0);
     runs[g] = Run{bt, bt->d_active + start, cnt, ng == 1 ? s : bt->workers[g], ng == 1, &next_event};
+    runs[g].n_ard = std::max(0, start + cnt - std::max(start, n_iso));
     start += cnt;
   }
   if (ng > 1) {
@@ -1163,6 +1177,8 @@ int submit_dense(SubmitCall& c, gpx_batch::PendingEval& pe) {
   // evaluating concurrently, its workgroups are dispatched ahead of the other batches' kernels
   const bool prio = knob_on(Knob::ContractPriority);
   Run cr{bt, bt->d_active, n_dense, s};
+  cr.n_ard = n_ard;
+  cr.ard_terms = c.max_terms(n_iso, n_dense);
   if (prio) {
     if (!bt->hp) {
       int lo = 0, hi = 0;
@@ -1175,7 +1191,7 @@ int submit_dense(SubmitCall& c, gpx_batch::PendingEval& pe) {
   }
   PhaseTimer& ct = *pe.ct;
   ct.mark();
-  contract(cr, c.max_terms(0, n_dense), pe.kev[0], pe.kev[1]);
+  contract(cr, c.max_terms(0, n_iso), pe.kev[0], pe.kev[1]);
   ct.mark();
   reduce(cr);
   if (prio) {

@@ -255,6 +255,10 @@ struct Run {
   // sized by band_fused_eval for the lanes it actually launches
   double** bcr_wsp = nullptr;
   size_t* bcr_capp = nullptr;
+  // a dense range: its last n_ard problems have specs with ARD terms (route_call and predict order
+  // them behind the isotropic ones), built and contracted by the ARD kernels
+  int n_ard = 0;
+  int ard_terms = 1;  // the most terms of an ARD problem's spec (contract's max_terms: the isotropic ones')
 };
 
 struct PhaseTimer {
@@ -311,6 +315,7 @@ struct Route {
   std::vector<int32_t> order;
   std::vector<int32_t> shadow_ids;
   int n_dense = 0, n_band = 0, n_fused = 0, n16 = 0, n_fused1 = 0, pband = 0;
+  int n_ard = 0;  // the dense problems whose spec has an ARD term: the last n_ard of [0, n_dense)
   int n_g16 = 0, g16_q[kBand16MaxQ] = {}, g16_n[kBand16MaxQ] = {};
   bool b16_p2 = false;
 };
@@ -323,6 +328,13 @@ void route_call(gpx_batch* bt, int n_active, const int32_t* active, const double
 struct RouteLimits { int plim = -1, q16lim = -1, q16wide = -1; bool fused_on = true; };
 // (the knobs and the rules derived from them, b16_inline_k .. bcr_max_problems: gpx_knobs.h)
 bool se1_spec(const gpx_kernel_spec& sp);     // one SquaredExponential term on one column
+bool ard_spec(const gpx_kernel_spec& sp);     // some term carries GPX_TERM_ARD: the dense ARD kernels
+// a term's parameter count (an ARD term: one lengthscale per active dim)
+int term_param_count(const gpx_term& tm);
+// why a spec cannot be taken for inputs of D columns (gpx_last_error's text), or null
+const char* spec_error(const gpx_kernel_spec& sp, int D);
+// K / cross-covariance build of a range whose last n_ard problems are ARD specs
+void build_range(const BuildArgs& a, int na, int n_ard, hipStream_t s);
 enum RouteKind { kRouteDense, kRouteShadow, kRouteBand, kRouteFused, kRouteBand16 };
 RouteLimits route_limits(const gpx_batch* bt);
 RouteKind route_one(const gpx_batch* bt, int b, const double* theta_row, const RouteLimits& L, int& w);

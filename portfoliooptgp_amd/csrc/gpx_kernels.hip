@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include "gpx_internal.h"
 #include "gpx_leaf.h"
+#include "gpx_kfun_ard.h"
 
 namespace gpx {
 
@@ -476,8 +477,9 @@ void gemm_kernel(GemmArgs a) {
   constexpr int MT = WT / 16;
   constexpr int NLD = BM * BK / 2 / 256;  // double2 chunks per thread per operand
   constexpr int kMainLds = 2 * 2 * BK * S;
-  constexpr bool kContractEpi = EPI == EPI_CONTRACT || EPI == EPI_CONTRACT1 || EPI == EPI_CONTRACT2;
-  constexpr int kEpiLds = (EPI == EPI_CONTRACT || EPI == EPI_CONTRACT1 || EPI == EPI_CONTRACT2)
+  constexpr bool kArdEpi = EPI == EPI_CONTRACT_ARD2 || EPI == EPI_CONTRACT_ARD;
+  constexpr bool kContractEpi = EPI == EPI_CONTRACT || EPI == EPI_CONTRACT1 || EPI == EPI_CONTRACT2 || kArdEpi;
+  constexpr int kEpiLds = kContractEpi
       ? 4 * 16 * WT + 2 * BM * GPX_MAX_DIM + 2 * BM + GPX_THETA_STRIDE + 64 : 0;
   __shared__ __attribute__((aligned(16))) double smem[kMainLds > kEpiLds ? kMainLds : kEpiLds];
 
@@ -811,6 +813,12 @@ void gemm_kernel(GemmArgs a) {
       if (slot >= 0) s = sred[slot] + sred[16 + slot] + sred[32 + slot] + sred[48 + slot];
       out[tid] = s;
     }
+  } else if constexpr (kArdEpi) {
+    // specs with ARD terms (gpx_kfun_ard.h): θ-indexed sums, one per lengthscale
+    ard_contract_tile<BM, (EPI == EPI_CONTRACT_ARD2 ? 2 : GPX_MAX_TERMS), MT>(
+        a.X + (long long)b * a.sX, a.vec + (long long)b * a.sVec, a.theta + b * GPX_THETA_STRIDE, a.specs + b,
+        a.D, a.nvalid[b], i0, j0, acc, smem,
+        a.partial + (long long)b * a.sPartial + (long long)tile * GPX_THETA_STRIDE);
   } else {  // EPI_COLSUMSQ
     double* scol = smem;  // [2][BN]
     __syncthreads();
@@ -873,6 +881,24 @@ static void launch_gemm_t(const GemmArgs& a0, bool ta, bool tb, int n_active, hi
   else hipLaunchKernelGGL((gemm_kernel<BM, true, true, EPI>), grid, dim3(256), 0, s, a);
 }
 
+// the ARD contraction (K⁻¹ = WᵀW: opA transposed, opB not): the tile size by the shape only, as the
+// isotropic contraction's
+static void launch_gemm_ard(const GemmArgs& a0, int epi, int n_active, hipStream_t s) {
+  GemmArgs a = a0;
+  a.n_active = n_active;
+  const int bm = gemm_tile(a, n_active);
+  const int ti = a.M / bm;
+  const int ntiles = ti * (ti + 1) / 2;
+  const int q = n_active / 8, r = n_active % 8;
+  dim3 grid(8 * (q * ntiles + (r * ntiles + 7) / 8));
+  auto k = bm == 128 ? (epi == EPI_CONTRACT_ARD2 ? gemm_kernel<128, true, false, EPI_CONTRACT_ARD2>
+                                                 : gemm_kernel<128, true, false, EPI_CONTRACT_ARD>)
+                     : (epi == EPI_CONTRACT_ARD2 ? gemm_kernel<64, true, false, EPI_CONTRACT_ARD2>
+                                                 : gemm_kernel<64, true, false, EPI_CONTRACT_ARD>);
+  if (a.ev_start) hipExtLaunchKernelGGL(k, grid, dim3(256), 0, s, a.ev_start, a.ev_stop, 0, a);
+  else hipLaunchKernelGGL(k, grid, dim3(256), 0, s, a);
+}
+
 void launch_gemm(const GemmArgs& a, int epi, bool ta, bool tb, int n_active, hipStream_t s) {
   // unreachable through the C ABI (shapes are checked against kGemmMaxLd at create/predict);
   // a silent zero-filled operand would be far worse than stopping here
@@ -880,6 +906,13 @@ void launch_gemm(const GemmArgs& a, int epi, bool ta, bool tb, int n_active, hip
     fprintf(stderr, "gpx: GEMM leading dimension %d/%d exceeds the buffer-load window (%lld)\n",
             a.lda, a.ldb, kGemmMaxLd);
     abort();
+  }
+  if (epi == EPI_CONTRACT_ARD2 || epi == EPI_CONTRACT_ARD) {
+    if (!ta || tb || !a.lower_only) {
+      fprintf(stderr, "gpx: the ARD contraction is the lower-tile WᵀW launch only\n");
+      abort();
+    }
+    return launch_gemm_ard(a, epi, n_active, s);
   }
   const int bm = gemm_tile(a, n_active);
   if (bm == 128) {

@@ -292,6 +292,10 @@ void route_call(gpx_batch* bt, int n_active, const int32_t* active, const double
   }
   rt.n16 = 0;
   for (int q = 1; q <= kBand16MaxQ; ++q) rt.n16 += (int)b16_ids[q].size();
+  // the dense class: isotropic specs first, then the ARD ones (their own build and contraction)
+  const auto first_ard = std::stable_partition(order.begin(), order.end(),
+                                               [&](int32_t b) { return !ard_spec(bt->specs[b]); });
+  rt.n_ard = (int)(order.end() - first_ard);
   rt.n_dense = (int)order.size();
   rt.n_band = (int)band_ids.size();
   rt.n_fused = (int)fused_ids.size() + rt.n16;
@@ -319,6 +323,49 @@ bool se1_spec(const gpx_kernel_spec& sp) {
   return sp.n_terms == 1 && sp.terms[0].kind == GPX_SE && sp.terms[0].dim_count == 1;
 }
 
+// a spec with an ARD term (GPX_TERM_ARD): never banded (band_kind refuses the flagged kind), always
+// the dense route's ARD kernels
+bool ard_spec(const gpx_kernel_spec& sp) {
+  for (int t = 0; t < sp.n_terms && t < GPX_MAX_TERMS; ++t)
+    if (sp.terms[t].kind & GPX_TERM_ARD) return true;
+  return false;
+}
+
+int term_param_count(const gpx_term& tm) {
+  const int kind = tm.kind & GPX_TERM_KIND_MASK;
+  const int np = (kind == GPX_RQ || kind == GPX_PERIODIC_SE) ? 3 : (kind == GPX_LINEAR ? 1 : 2);
+  return (tm.kind & GPX_TERM_ARD) ? np - 1 + tm.dim_count : np;
+}
+
+const char* spec_error(const gpx_kernel_spec& sp, int D) {
+  if (sp.n_terms < 1 || sp.n_terms > GPX_MAX_TERMS || sp.n_params < 1 || sp.n_params >= GPX_THETA_STRIDE)
+    return "bad kernel spec";
+  int staged = 0;
+  bool ard = false, raw = false;
+  for (int t = 0; t < sp.n_terms; ++t) {
+    const gpx_term& tm = sp.terms[t];
+    const int kind = tm.kind & GPX_TERM_KIND_MASK;
+    if ((tm.kind & ~(GPX_TERM_ARD | GPX_TERM_KIND_MASK)) != 0 || kind < GPX_SE || kind > GPX_LINEAR ||
+        tm.dim_start < 0 || tm.dim_count < 1 || tm.dim_start + tm.dim_count > D || tm.param_offset < 0)
+      return "bad kernel term";
+    if (tm.kind & GPX_TERM_ARD) {
+      if (kind > GPX_RQ) return "GPX_TERM_ARD is valid with the SE, Matern, Exponential and RationalQuadratic kinds only";
+      if (tm.dim_count < 2) return "GPX_TERM_ARD needs dim_count >= 2 (one active dim: the plain term)";
+      ard = true;
+    }
+    if (tm.param_offset + term_param_count(tm) > sp.n_params) return "bad kernel term";
+    if (kind <= GPX_RQ) staged += tm.dim_count;
+    else raw = true;
+  }
+  // (the ARD kernels stage every stationary term's scaled rows, and the raw rows for Linear /
+  // Periodic terms, in GPX_MAX_DIM doubles per row)
+  if (ard && sp.n_params + 1 > GPX_THETA_STRIDE - 1)
+    return "an ARD spec may use GPX_THETA_STRIDE - 1 columns of the theta row (kernel parameters + noise)";
+  if (ard && staged + (raw ? D : 0) > GPX_MAX_DIM)
+    return "an ARD spec's stationary terms cover more than GPX_MAX_DIM input columns in total";
+  return nullptr;
+}
+
 }  // namespace gpx
 
 extern "C" {
@@ -336,6 +383,7 @@ int gpx_batch_band_width(gpx_batch* bt, int n_rows, const int32_t* rows, const d
       p_out[i] = -2;
       continue;
     }
+    // (a spec with an ARD term: band_width's −1, dense)
     const int p = plim >= 0 ? band_width(bt, b, theta + (size_t)b * GPX_THETA_STRIDE) : -1;
     p_out[i] = (p >= 0 && p <= plim) ? p : -1;
   }

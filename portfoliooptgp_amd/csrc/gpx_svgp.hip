@@ -139,6 +139,7 @@ int gpx_svgp_create(gpx_ctx* ctx, int N, int M, int D, const double* X, const do
   if (N < 1 || M < 1 || D < 1 || D > GPX_MAX_DIM || !X || !Y || !spec || !(num_data > 0.0) ||
       n_total < N)
     return fail(ctx, GPX_BAD_ARG, "bad svgp dimensions or null pointer");
+  if (ard_spec(*spec)) return fail(ctx, GPX_BAD_ARG, "ARD terms (GPX_TERM_ARD) are served by the gpx_batch_* entry points only");
   HIPX(ctx, hipSetDevice(ctx->device));
   gpx_svgp* sv = new gpx_svgp();
   sv->ctx = ctx; sv->N = N; sv->M = M; sv->D = D; sv->X = X; sv->Y = Y; sv->spec = *spec;

@@ -124,9 +124,16 @@ def fit_cost(n: int, band_blocks: Optional[int] = None, band16_q: Optional[int] 
     return _K64 * float(n) * w * w
 
 
-def series_cost(x) -> float:
+def series_cost(x, kernel=None) -> float:
     """fit_cost of a series for the default fitter (SE at GPflow's default ℓ = 1), on the path
-    the device routes it to at that ℓ."""
+    the device routes it to at that ℓ. ``kernel``: the fit's kernel when it is not the default
+    one; a kernel with ARD lengthscales over several dims always runs dense."""
+    if kernel is not None:
+        from .kernels import compile_spec
+        xa = np.asarray(x)
+        spec = compile_spec(kernel, 1 if xa.ndim == 1 else int(xa.shape[1]))
+        if any(spec.terms[t].kind & 0x100 for t in range(spec.n_terms)):  # (GPX_TERM_ARD, include/gpx.h)
+            return fit_cost(len(x))
     return fit_cost(len(x), band_blocks_estimate(x), band16_estimate(x))
 
 
@@ -370,7 +377,7 @@ def gpu_fit_shard(series, horizons, width: int = 32, maxiter: int = 100):
     for m, r, (mean, var) in zip(ms, res, preds):
         mean, var = mean.cpu().numpy(), var.cpu().numpy()
         out.append(dict(loss=float(r.fun), nfev=int(r.nfev),
-                        theta=[p.value for p in m.kernel.parameters],
+                        theta=m.kernel.theta_values(),
                         mean=np.asarray(mean).reshape(-1), var=np.asarray(var).reshape(-1)))
     return out
 

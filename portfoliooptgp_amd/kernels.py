@@ -7,13 +7,20 @@ Exponential, SE+Matern12, Exponential+Periodic(SE)+Linear, Exponential+Periodic(
 SE*Matern12) and Multi-Input_GPR/main.py:118-135 (Exponential(active_dims) *
 Exponential(active_dims)). Parameter order = GPflow's tf.Module flattening order
 (sorted attribute names; Sum/Product kernels in list order).
+
+ARD: the stationary kernels take ``lengthscales`` as a scalar or as a 1-D sequence with one entry
+per active dim (``kernel.ard`` is then True, as in GPflow). The vector is one trainable variable;
+in the θ row it is flattened where the scalar sits: ``[ℓ_0 … ℓ_{dn−1}, σ²]``, RationalQuadratic
+``[α, ℓ_0 … ℓ_{dn−1}, σ²]``. Served by ``models.GPR`` (the dense route); see DESIGN.md §3h.
 """
 from __future__ import annotations
 
 from typing import List, Optional, Sequence, Tuple
 
+import numpy as np
+
 from . import _native as N
-from .parameter import Parameter
+from .parameter import Parameter, VectorParameter
 
 
 def _normalise_active_dims(active_dims) -> Optional[Tuple[int, int]]:
@@ -57,6 +64,27 @@ class Kernel:
     def _param_paths(self, prefix: str) -> List[Tuple[str, Parameter]]:
         raise NotImplementedError
 
+    def _theta_slots(self) -> List[Tuple[object, Optional[int]]]:
+        """The kernel's θ columns in order: (parameter, entry) per column — entry None for a
+        scalar parameter, the index into its vector for an ARD lengthscale."""
+        out: List[Tuple[object, Optional[int]]] = []
+        for p in self.parameters:
+            if isinstance(p, VectorParameter):
+                out.extend((p, e) for e in range(p.size))
+            else:
+                out.append((p, None))
+        return out
+
+    def theta_values(self) -> List[float]:
+        """Constrained values of the θ columns (``_theta_slots`` order)."""
+        out: List[float] = []
+        for p in self.parameters:
+            if isinstance(p, VectorParameter):
+                out.extend(p.value.tolist())
+            else:
+                out.append(p.value)
+        return out
+
     def _terms(self) -> List["Kernel"]:
         return [self]
 
@@ -71,14 +99,19 @@ class Kernel:
         return Product([self, other])
 
     def __repr__(self) -> str:
+        def show(p):
+            if isinstance(p, VectorParameter):
+                return "[" + ", ".join(f"{v:.6g}" for v in p.value.tolist()) + "]"
+            return f"{p.value:.6g}"
         return f"<{type(self).__name__} " + ", ".join(
-            f"{n}={p.value:.6g}" for n, p in self._param_paths("")) + ">"
+            f"{n}={show(p)}" for n, p in self._param_paths("")) + ">"
 
 
 class _Term(Kernel):
     kind = 0
+    ard = False
 
-    def _spec_term(self, D: int, offset: int) -> N.GpxTerm:
+    def _active(self, D: int) -> Tuple[int, int]:
         if self._dims is None:
             start, count = 0, D
         else:
@@ -87,16 +120,44 @@ class _Term(Kernel):
                 count = D - start
         if start < 0 or count < 1 or start + count > D:
             raise ValueError(f"{self.name}: active_dims {self.active_dims} out of range for D={D}")
+        return start, count
+
+    def _spec_term(self, D: int, offset: int) -> N.GpxTerm:
+        start, count = self._active(D)
         return N.GpxTerm(self.kind, start, count, offset)
 
 
 class Stationary(_Term):
-    """IsotropicStationary: scalar lengthscale, params ordered [lengthscales, variance]."""
+    """Stationary kernels of r = |x − x'| / ℓ: a scalar lengthscale (isotropic) or a vector with
+    one entry per active dim (ARD); params ordered [lengthscales, variance]."""
 
     def __init__(self, variance=1.0, lengthscales=1.0, active_dims=None, name=None):
         super().__init__(active_dims=active_dims, name=name)
         self.variance = Parameter(variance, name="variance")
-        self.lengthscales = Parameter(lengthscales, name="lengthscales")
+        if np.ndim(lengthscales) == 0:
+            self.lengthscales = Parameter(lengthscales, name="lengthscales")
+        else:
+            if np.ndim(lengthscales) != 1:
+                raise ValueError(f"{self.name}: ARD lengthscales must be a 1-D sequence, one entry per active dim")
+            self.lengthscales = VectorParameter(lengthscales, name="lengthscales")
+            # (an open-ended slice or 'all dims' is checked against D at compile_spec)
+            if self._dims is not None and self._dims[1] >= 0 and self._dims[1] != self.lengthscales.size:
+                raise ValueError(f"{self.name}: {self.lengthscales.size} lengthscales for "
+                                 f"{self._dims[1]} active dims")
+
+    @property
+    def ard(self) -> bool:
+        """True when ``lengthscales`` is a vector (gpflow.kernels.Stationary.ard)."""
+        return isinstance(self.lengthscales, VectorParameter)
+
+    def _spec_term(self, D: int, offset: int) -> N.GpxTerm:
+        start, count = self._active(D)
+        if not self.ard:
+            return N.GpxTerm(self.kind, start, count, offset)
+        if self.lengthscales.size != count:
+            raise ValueError(f"{self.name}: {self.lengthscales.size} lengthscales for {count} active dims")
+        # ARD over one active dim is the plain term (the same θ layout: it keeps the banded routes)
+        return N.GpxTerm(self.kind | (N.GPX_TERM_ARD if count > 1 else 0), start, count, offset)
 
     @property
     def parameters(self):
@@ -156,6 +217,8 @@ class Linear(_Term):
 
     def __init__(self, variance=1.0, active_dims=None, name=None):
         super().__init__(active_dims=active_dims, name=name)
+        if np.ndim(variance) != 0:
+            raise NotImplementedError("Linear takes a scalar variance (a vector, ARD, variance is not provided)")
         self.variance = Parameter(variance, name="variance")
 
     @property
@@ -175,6 +238,8 @@ class Periodic(_Term):
         base_kernel = base_kernel if base_kernel is not None else SquaredExponential()
         if type(base_kernel) is not SquaredExponential:
             raise NotImplementedError("Periodic is implemented for a SquaredExponential base kernel")
+        if base_kernel.ard:
+            raise NotImplementedError("Periodic over an ARD base kernel is not provided (scalar lengthscales only)")
         super().__init__(active_dims=base_kernel.active_dims, name=name)
         self.base_kernel = base_kernel
         self.period = Parameter(period, name="period")
@@ -248,8 +313,27 @@ def compile_spec(kernel: Kernel, D: int) -> N.GpxKernelSpec:
     off = 0
     for t, term in enumerate(terms):
         spec.terms[t] = term._spec_term(D, off)
-        off += len(term.parameters)
+        off += len(term._theta_slots())
     if off + 1 > N.GPX_THETA_STRIDE:
-        raise NotImplementedError("too many kernel parameters")
+        raise NotImplementedError(
+            f"too many kernel parameters: the θ row holds {N.GPX_THETA_STRIDE} values, this kernel needs "
+            f"{off} + the noise variance")
+    if any(spec.terms[t].kind & N.GPX_TERM_ARD for t in range(len(terms))):
+        # an ARD spec leaves the row's last column free (include/gpx.h); the ARD kernels stage every
+        # stationary term's scaled inputs in GPX_MAX_DIM values per row (plus D for Linear / Periodic)
+        if off + 1 > N.GPX_THETA_STRIDE - 1:
+            raise NotImplementedError(
+                f"too many kernel parameters for an ARD kernel: the θ row holds {N.GPX_THETA_STRIDE} values, "
+                f"of which an ARD kernel and the noise variance may use {N.GPX_THETA_STRIDE - 1}; this one "
+                f"needs {off + 1}")
+        staged = sum(spec.terms[t].dim_count for t, k in enumerate(terms) if isinstance(k, Stationary))
+        if staged + (D if any(not isinstance(k, Stationary) for k in terms) else 0) > N.GPX_MAX_DIM:
+            raise NotImplementedError(
+                f"an ARD kernel's stationary terms may cover at most {N.GPX_MAX_DIM} input columns in total")
     spec.n_params = off
     return spec
+
+
+def has_ard(kernel: Kernel) -> bool:
+    """True when some term of ``kernel`` has vector lengthscales."""
+    return any(getattr(k, "ard", False) for k in kernel._terms())

@@ -21,10 +21,18 @@ import torch
 
 from . import _native as N
 from .engine import Engine, default_device, solo_engine
-from .kernels import Kernel, compile_spec
+from .kernels import Kernel, compile_spec, has_ard
 from .likelihoods import Gaussian, StudentT
 from .mean_functions import MeanFunction, Zero
-from .parameter import ArrayParameter, Parameter
+from .parameter import ArrayParameter, Parameter, VectorParameter, sigmoid
+
+
+def _refuse_ard(kernel: Kernel, model: str) -> None:
+    """ARD lengthscales are served by models.GPR; the sparse / variational models evaluate K
+    through the isotropic device functions."""
+    if has_ard(kernel):
+        raise NotImplementedError(f"{model} takes kernels with scalar lengthscales: ARD (vector) "
+                                  "lengthscales are implemented for models.GPR")
 
 
 class GPR:
@@ -106,13 +114,12 @@ class GPR:
         """Constrained θ in the gpx layout: kernel params, then σn² at index n_params, then the
         mean function's coefficients (gpx_mean_spec order)."""
         row = np.ones(N.GPX_THETA_STRIDE, dtype=np.float64)
-        kp = self.kernel.parameters
-        for i, p in enumerate(kp):
-            row[i] = p.value
-        row[len(kp)] = self.likelihood.variance.value
+        kv = self.kernel.theta_values()  # (an ARD lengthscale vector: one column per entry)
+        row[:len(kv)] = kv
+        row[len(kv)] = self.likelihood.variance.value
         if self._mean is not None:
             c = self._mean.coefficients()
-            row[len(kp) + 1: len(kp) + 1 + len(c)] = c
+            row[len(kv) + 1: len(kv) + 1 + len(c)] = c
         return row
 
     def mean_spec(self):
@@ -166,34 +173,43 @@ class GPR:
         return closure
 
     def _variable_map(self, variables):
-        """(variables, θ-row index of each flattened variable entry, its Parameter), cached for
-        the variables object an optimiser passes on every call (kernel parameters, then σn² at
-        n_params, then the mean function's coefficients). An array variable (a mean parameter)
-        takes one consecutive column per entry, so ``rows`` follows the optimiser's flattened x."""
+        """(variables, θ-row index of each flattened variable entry, its Parameter, its entry
+        index), cached for the variables object an optimiser passes on every call (kernel
+        parameters, then σn² at n_params, then the mean function's coefficients). An array
+        variable (a mean parameter, an ARD lengthscale vector) takes one consecutive column per
+        entry, so ``rows`` follows the optimiser's flattened x; ``ents`` is the entry's index
+        into a VectorParameter (None for every other parameter)."""
         cache = getattr(self, "_grad_map", None)
         if cache is None or cache[0] is not variables:
-            pindex = {id(p): i for i, p in enumerate(self.kernel.parameters)}
-            nk = len(self.kernel.parameters)
+            pindex, nk = {}, 0  # parameter -> (first column, columns)
+            for p in self.kernel.parameters:
+                cnt = p.size if isinstance(p, VectorParameter) else 1
+                pindex[id(p)] = (nk, cnt)
+                nk += cnt
             mindex, o = {}, nk + 1
             for p in (self._mean.parameters if self._mean is not None else ()):
                 mindex[id(p)] = (o, int(np.prod(p.shape)))
                 o += mindex[id(p)][1]
-            rows, params = [], []
+            rows, params, ents = [], [], []
             for v in variables:
                 p = v._param
                 if p is self.likelihood.variance:
                     rows.append(nk)
                     params.append(p)
+                    ents.append(None)
                 elif id(p) in pindex:
-                    rows.append(pindex[id(p)])
-                    params.append(p)
+                    c0, cnt = pindex[id(p)]
+                    rows.extend(range(c0, c0 + cnt))
+                    params.extend([p] * cnt)
+                    ents.extend(range(cnt) if isinstance(p, VectorParameter) else [None])
                 elif id(p) in mindex:
                     c0, cnt = mindex[id(p)]
                     rows.extend(range(c0, c0 + cnt))
                     params.extend([p] * cnt)
+                    ents.extend([None] * cnt)
                 else:
                     raise ValueError(f"variable {v.name} is not a parameter of this model")
-            cache = self._grad_map = (variables, rows, params)
+            cache = self._grad_map = (variables, rows, params, ents)
         return cache
 
     def theta_layout(self, variables, transforms: bool = False):
@@ -201,7 +217,7 @@ class GPR:
         entry, for the batched driver's native θ / chain-rule helpers (gpx_host_theta_rows /
         _loss_grad_u). With ``transforms`` a third array, int32 [P]: the entry's transform code
         (0 softplus + Shift, 1 identity: a mean coefficient; gpx_host_theta_rows_t)."""
-        _, rows, params = self._variable_map(variables)
+        _, rows, params, _ = self._variable_map(variables)
         cols = np.asarray(rows, dtype=np.int32)
         ident = [isinstance(p, ArrayParameter) for p in params]
         lower = np.asarray([0.0 if i else p.lower for p, i in zip(params, ident)], dtype=np.float64)
@@ -215,11 +231,15 @@ class GPR:
         if lml is None:
             lml, grad_theta = self._lml_and_grad_theta()
         variables = self.trainable_variables if variables is None else variables
-        _, rows, params = self._variable_map(variables)
+        _, rows, params, ents = self._variable_map(variables)
         g = np.empty(len(rows), dtype=np.float64)
-        for k, (r, p) in enumerate(zip(rows, params)):
-            # (a mean coefficient's transform is the identity: ∂θ/∂u = 1)
-            g[k] = -grad_theta[r] if isinstance(p, ArrayParameter) else -grad_theta[r] * p.dtheta_du()
+        for k, (r, p, e) in enumerate(zip(rows, params, ents)):
+            if isinstance(p, ArrayParameter):  # (a mean coefficient's transform is the identity: ∂θ/∂u = 1)
+                g[k] = -grad_theta[r]
+            elif e is not None:                # (an ARD lengthscale: its own sigmoid(u_d))
+                g[k] = -grad_theta[r] * sigmoid(p.unconstrained[e])
+            else:
+                g[k] = -grad_theta[r] * p.dtheta_du()
         return -float(lml), g
 
     # ---------------------------------------------------------------- prediction ------
@@ -299,6 +319,7 @@ class SVGP:
             raise NotImplementedError("SVGP supports GPflow's defaults: one latent GP, full q_sqrt, whiten=True")
         if not isinstance(likelihood, Gaussian):
             raise NotImplementedError("SVGP supports the Gaussian likelihood")
+        _refuse_ard(kernel, "SVGP")
         self.kernel = kernel
         self.likelihood = likelihood
         self.inducing_variable = (inducing_variable if isinstance(inducing_variable, InducingPoints)
@@ -482,6 +503,7 @@ class SGPR:
         if not isinstance(likelihood, Gaussian):
             raise NotImplementedError("SGPR supports the Gaussian likelihood")
         self.data = (Xt, Yt)
+        _refuse_ard(kernel, "SGPR")
         self.kernel = kernel
         self.likelihood = likelihood
         self.mean_function = mean_function
@@ -634,6 +656,7 @@ class VGP:
             raise ValueError("VGP needs at least one training point (X has 0 rows)")
         n = int(Xt.shape[0])
         self.data = (Xt, Yt)
+        _refuse_ard(kernel, "VGP")
         self.kernel = kernel
         self.likelihood = likelihood
         self.mean_function = mean_function

@@ -132,6 +132,109 @@ class Parameter:
 
 
 # ----------------------------------------------------------------------------------------
+# positive vector parameters (ARD lengthscales)
+# ----------------------------------------------------------------------------------------
+class VectorVariable:
+    """Unconstrained tf.Variable-like handle of a VectorParameter (shape ``(n,)``)."""
+
+    def __init__(self, param: "VectorParameter"):
+        self._param = param
+
+    @property
+    def name(self) -> str:
+        return f"{self._param.name}:0"
+
+    @property
+    def shape(self):
+        return self._param._u.shape
+
+    @property
+    def dtype(self):
+        return np.float64
+
+    @property
+    def trainable(self) -> bool:
+        return self._param.trainable
+
+    def numpy(self) -> np.ndarray:
+        return self._param._u.copy()
+
+    def assign(self, u) -> None:
+        self._param.set_unconstrained(u)
+
+    def __repr__(self) -> str:
+        return f"<VectorVariable {self.name} u={self._param._u!r}>"
+
+
+class VectorParameter:
+    """A 1-D positive parameter, θ_d = lower + softplus(u_d) entry by entry (GPflow's
+    ``Parameter(value, transform=positive())`` with a vector value: an ARD ``lengthscales``).
+    One trainable variable of shape ``(n,)``; in a GPR's θ row its entries take ``n`` consecutive
+    columns, each with the softplus transform code and its own sigmoid(u_d) in the chain rule.
+    Deliberately not an ``ArrayParameter`` (those mean the identity / triangular transforms)."""
+
+    def __init__(self, value, lower: float = 0.0, trainable: bool = True, name: str = "parameter"):
+        self.lower = float(lower)
+        self.trainable = bool(trainable)
+        self.name = name
+        v = np.array(value, dtype=np.float64)
+        if v.ndim != 1 or v.size < 1:
+            raise ValueError(f"{name}: a vector parameter needs a 1-D value with at least one entry")
+        self._u = np.empty(v.shape, dtype=np.float64)
+        self.assign(v)
+        self._variable = VectorVariable(self)
+
+    # --- constrained view -------------------------------------------------------------
+    @property
+    def value(self) -> np.ndarray:
+        return np.array([self.lower + softplus(u) for u in self._u.tolist()], dtype=np.float64)
+
+    def numpy(self) -> np.ndarray:
+        return self.value
+
+    def assign(self, value) -> None:
+        v = np.asarray(value, dtype=np.float64)
+        if v.shape != self._u.shape:
+            raise ValueError(f"{self.name}: value of shape {v.shape} assigned to a parameter of shape {self._u.shape}")
+        if not np.all(v > self.lower):  # (nan fails too)
+            raise ValueError(f"{self.name}: every value must be > {self.lower} (positive transform), got {v}")
+        self._u = np.array([softplus_inverse(t - self.lower) for t in v.tolist()], dtype=np.float64)
+
+    @property
+    def shape(self):
+        return self._u.shape
+
+    @property
+    def size(self) -> int:
+        return int(self._u.size)
+
+    # --- unconstrained view -----------------------------------------------------------
+    @property
+    def unconstrained(self) -> np.ndarray:
+        return self._u
+
+    def set_unconstrained(self, u) -> None:
+        self._u = np.array(u, dtype=np.float64).reshape(self._u.shape)
+
+    @property
+    def unconstrained_variable(self) -> VectorVariable:
+        return self._variable
+
+    def dtheta_du(self) -> np.ndarray:
+        return np.array([sigmoid(u) for u in self._u.tolist()], dtype=np.float64)
+
+    @property
+    def transform_name(self) -> str:
+        return "Softplus" if self.lower == 0.0 else "Softplus + Shift"
+
+    def __array__(self, dtype=None, copy=None):
+        return np.asarray(self.value, dtype=dtype or np.float64)
+
+    def __repr__(self) -> str:
+        return f"<VectorParameter {self.name}={self.value!r} trainable={self.trainable}>"
+
+
+# ----------------------------------------------------------------------------------------
 # array-valued parameters (SVGP: inducing inputs Z, q_mu, q_sqrt)
 # ----------------------------------------------------------------------------------------
 _TRI_CACHE = {}

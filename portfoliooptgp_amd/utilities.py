@@ -4,12 +4,12 @@ from __future__ import annotations
 
 import numpy as np
 
-from .parameter import ArrayParameter, Parameter
+from .parameter import ArrayParameter, Parameter, VectorParameter
 
 
 def set_trainable(obj, flag: bool) -> None:
     """Set ``trainable`` on a Parameter or on every Parameter of a kernel/likelihood/model."""
-    if isinstance(obj, (Parameter, ArrayParameter)):
+    if isinstance(obj, (Parameter, ArrayParameter, VectorParameter)):
         obj.trainable = bool(flag)
         return
     params = getattr(obj, "parameters", None)
@@ -28,6 +28,9 @@ def summary_rows(model):
             v = p.value
             rows.append((name, "Parameter", p.transform_name, p.trainable, str(tuple(v.shape)), "float64",
                          np.array2string(v.ravel()[:3], precision=4) + ("..." if v.size > 3 else "")))
+        elif isinstance(p, VectorParameter):  # (an ARD lengthscale: the whole vector, as GPflow prints it)
+            rows.append((name, "Parameter", p.transform_name, p.trainable, str(tuple(p.shape)), "float64",
+                         np.array2string(p.value, precision=5)))
         else:
             rows.append((name, "Parameter", p.transform_name, p.trainable, "()", "float64", p.value))
     return rows
