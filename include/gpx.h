@@ -424,6 +424,23 @@ typedef struct gpx_svgp gpx_svgp;
 int gpx_svgp_create(gpx_ctx* ctx, int N, int M, int D, const double* X, const double* Y,
                     const gpx_kernel_spec* spec, double num_data, long long n_total,
                     gpx_svgp** out);
+/* The same model with a Gaussian or StudentT likelihood (GPX_LIK_*, below), evaluated by the
+ * per-point route: the marginal (μ_n, v_n) of every data row, GPflow's variational expectation of
+ * it (closed form for the Gaussian, the 20-point Gauss–Hermite rule for StudentT, the arithmetic of
+ * gpx_vgp) and per-row weights through the same M x M algebra — three M²N GEMM passes plus element
+ * passes over M x N; one more M x N buffer than gpx_svgp_create. An object from here takes this
+ * route for BOTH likelihoods: with GPX_LIK_GAUSSIAN it computes the ELBO of gpx_svgp_create by the
+ * general route (equal up to summation order; gpx_svgp_create keeps its closed-form path and its
+ * bits). theta[n_params] is the likelihood parameter, finite and > 0: the Gaussian variance or the
+ * StudentT scale; grad_theta[n_params] is its gradient. df (StudentT only; fixed) must be finite and
+ * > 0 at create; predict with add_noise adds scale²·df/(df − 2) and needs df > 2 (GPX_BAD_ARG
+ * otherwise). The partials / bind_partials / eval_local / eval_finish / elbo_grad / predict /
+ * destroy calls below serve both kinds of object; the partial buffer has the same length and layout
+ * except its scalars, which are Σ ve, Σ ∂ve/∂φ, n_local here. Shards of one model must all come
+ * from the same create call. */
+int gpx_svgp_create_lik(gpx_ctx* ctx, int N, int M, int D, const double* X, const double* Y,
+                        const gpx_kernel_spec* spec, double num_data, long long n_total,
+                        int likelihood /* GPX_LIK_* */, double df, gpx_svgp** out);
 int gpx_svgp_destroy(gpx_svgp* svgp);
 /* the partial-sum buffer (device, fp64, len doubles) and a way to substitute a caller-owned
  * one (e.g. a torch tensor that torch.distributed all-reduces in place) */

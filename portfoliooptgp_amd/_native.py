@@ -45,7 +45,7 @@ EXPORTED_SYMBOLS = (
     "gpx_batch_wave_trace", "gpx_batch_wave_trace_read", "gpx_batch_band_class",
     "gpx_batch_set_deferred", "gpx_batch_deferred_wait", "gpx_batch_deferred_rows",
     "gpx_batch_set_band_route",
-    "gpx_svgp_create", "gpx_svgp_destroy", "gpx_svgp_partials", "gpx_svgp_bind_partials",
+    "gpx_svgp_create", "gpx_svgp_create_lik", "gpx_svgp_destroy", "gpx_svgp_partials", "gpx_svgp_bind_partials",
     "gpx_svgp_eval_local", "gpx_svgp_eval_finish", "gpx_svgp_elbo_grad", "gpx_svgp_predict",
     "gpx_sgpr_create", "gpx_sgpr_destroy", "gpx_sgpr_elbo_grad", "gpx_sgpr_predict",
     "gpx_vgp_create", "gpx_vgp_destroy", "gpx_vgp_elbo_grad", "gpx_vgp_predict",
@@ -210,6 +210,10 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.gpx_svgp_create.restype = c_int
         lib.gpx_svgp_create.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, spec_p,
                                         c_double, ctypes.c_longlong, ctypes.POINTER(c_void_p)]
+        lib.gpx_svgp_create_lik.restype = c_int
+        lib.gpx_svgp_create_lik.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, spec_p,
+                                            c_double, ctypes.c_longlong, c_int, c_double,
+                                            ctypes.POINTER(c_void_p)]
         lib.gpx_svgp_destroy.restype = c_int
         lib.gpx_svgp_destroy.argtypes = [c_void_p]
         lib.gpx_svgp_partials.restype = c_int

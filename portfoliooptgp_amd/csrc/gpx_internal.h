@@ -440,4 +440,42 @@ void launch_vgp_quad(const VgpQuadArgs& a, hipStream_t s);
 int vgp_quad_blocks(int npad);
 void launch_vgp_final(const VgpFinalArgs& a, hipStream_t s);
 
+// ---- SVGP, per-point route (gpx_svgp.hip; kernels in gpx_svgp_lik_kernels.hip) ----------
+// Kmn and Q = P·Kmn are row-major [rows][ld]; columns n >= ncols_valid are padding (Kmn is zero
+// there, so every column sum is zero and v = 0).
+// Column variance as m-slice partials: part[b][n] = Σ_{m in slice b} Kmn[m,n]·Q[m,n], plus
+// k(x_n, x_n) in slice 0 for n < n; all ld columns of every slice are written.
+struct SvgpColvarArgs {
+  const double* Kmn; const double* Q; int ld; int rows; int slices;   // rows % (4·slices) == 0
+  const double* X; int D; int n;
+  const DevSpec* spec; const double* theta;
+  double* part;            // [slices][ld]
+};
+// VgpQuadArgs' expectation with the minibatch scale folded in: gmu = s ∂ve/∂μ, gv = s ∂ve/∂v
+// ([npad], zero beyond n: the quadrature is not evaluated there); block partials
+// [svgp_lik_quad_blocks(npad)][2]: Σ ve, Σ ∂ve/∂φ (unscaled).
+struct SvgpLikQuadArgs {
+  VgpQuadArgs q;
+  double scale;            // num_data / n_total
+};
+// Y[m,n] = 2·Y[m,n]·gv[n] in place and Ks[m,n] = Kmn[m,n]·gv[n], all rows × ld entries
+struct SvgpColscaleArgs {
+  const double* Kmn; double* Y; double* Ks; int ld; int rows;   // rows % 4 == 0
+  const double* gv;
+};
+// Σ_n gv[n] ∂k(x_n, x_n)/∂θ as block partials [svgp_lik_knn_blocks(n)][16] (θ layout)
+struct SvgpKnnArgs {
+  const double* X; int D; int n;
+  const double* gv;
+  const DevSpec* spec; const double* theta;
+  double* part;
+};
+int svgp_colvar_slices(int rows, int ld);   // m-slices that put more than one wave on every SIMD
+void launch_svgp_colvar(const SvgpColvarArgs& a, hipStream_t s);
+void launch_svgp_lik_quad(const SvgpLikQuadArgs& a, hipStream_t s);
+int svgp_lik_quad_blocks(int npad);
+void launch_svgp_colscale(const SvgpColscaleArgs& a, hipStream_t s);
+void launch_svgp_knn(const SvgpKnnArgs& a, hipStream_t s);
+int svgp_lik_knn_blocks(int n);
+
 }  // namespace gpx

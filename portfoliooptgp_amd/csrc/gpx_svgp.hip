@@ -14,6 +14,18 @@
 // finite differences). The data-size work is two MFMA GEMMs of M²N (split-K SYRK for G,
 // Y = 2c P Kmn) plus O(MN) element passes; everything after the per-shard partial sums is
 // O(M³) and replicated, so N shards over GPUs with one all-reduce of the partial buffer.
+//
+// The per-point route (objects of gpx_svgp_create_lik; Gaussian or Student-t likelihood with
+// parameter φ): v_n is formed for every row, the variational expectation ve(μ_n, v_n, y_n) is
+// vgp_quad_kernel's, and per-row weights replace the uniform c:
+//   Q = P Kmn,   v_n = k_nn + Σ_m Kmn[m,n] Q[m,n],   E = Σ_n ve,   ELBO = s E − KL
+//   g_μ = s ∂ve/∂μ,  g_v = s ∂ve/∂v,  ∂ELBO/∂φ = s Σ ∂ve/∂φ
+//   K̄mn = u g_μᵀ + 2 Q diag(g_v),   G_w = Kmn diag(g_v) Kmnᵀ,   Ĝ_w = W G_w Wᵀ
+//   ∂θ = Σ K̄mn ∘ ∂Kmn + Σ K̄mm ∘ ∂Kmm + Σ_n g_v,n ∂k_nn/∂θ
+// and the O(M³) tail above runs unchanged on G := G_w with 2c := 2 (its trace is not used). g_v
+// takes both signs under the Student-t, so G_w is a product of the column-scaled copy
+// Ks = Kmn diag(g_v) with Kmn, not a SYRK. Padding columns n >= N: Kmn is zero there, so v = 0;
+// the quadrature is not evaluated (it divides by √(2v)) and g_μ = g_v = 0 are written.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -25,7 +37,7 @@ using namespace gpx;
 
 namespace {
 constexpr double kJitter = 1e-6;  // gpflow.config.default_jitter()
-constexpr int kScalars = 4;       // Σ(y−μ)², Σ k_nn, n_local, 0
+constexpr int kScalars = 4;       // Σ(y−μ)², Σ k_nn, n_local, 0  (per-point route: Σ ve, Σ ∂ve/∂φ, n_local, 0)
 }  // namespace
 
 struct gpx_svgp {
@@ -59,6 +71,16 @@ struct gpx_svgp {
   double h_nloc = 0.0;
   int h_info = 0;
   bool local_done = false;
+  // the per-point route (gpx_svgp_create_lik): likelihood, its constant, and the buffers only
+  // these objects allocate
+  bool per_point = false;
+  int lik = GPX_LIK_GAUSSIAN, slices = 1;
+  double df = 3.0, c0 = 0.0;
+  double *Ks = nullptr;                      // [Mp][Ncols] Kmn diag(g_v)
+  double *v = nullptr, *gv = nullptr;        // [Ncols]
+  double *vpart = nullptr;                   // [slices][Ncols]
+  double *pq = nullptr, *pknn = nullptr;     // block partials of the quadrature / weighted k_nn pass
+  std::vector<double> h_thdev;               // predict_y: the θ row with the added variance in the noise slot
 };
 
 namespace {
@@ -118,6 +140,51 @@ void factor_u(gpx_svgp* sv, hipStream_t s) {
 
 bool single_term(const gpx_svgp* sv) { return sv->spec.n_terms == 1; }
 
+// Kmn = k(Z, X) (rows ≥ M and columns ≥ N are zero)
+void build_kmn(gpx_svgp* sv, hipStream_t s) {
+  BuildArgs ba{};
+  ba.active = sv->kmm->d_active; ba.specs = sv->kmm->d_specs; ba.theta = sv->d_theta;
+  ba.nvalid = sv->kmm->d_n; ba.X = sv->dZ; ba.sX = 0; ba.X2 = sv->X; ba.sX2 = 0; ba.D = sv->D;
+  ba.m2 = sv->N; ba.out = sv->Kmn; ba.sOut = 0; ba.ldo = sv->Ncols; ba.rows = sv->Mp; ba.cols = sv->Ncols;
+  ba.symmetric = 0; ba.rows_valid = 0;
+  launch_build(ba, 1, s);
+}
+
+// The M×M chain on stream sa: W = L⁻¹, u = Wᵀ q_mu, S − I = q_sqrt q_sqrtᵀ − I, P = Wᵀ (S − I) W
+void mm_chain(gpx_svgp* sv, hipStream_t sa) {
+  const int M = sv->M, Mp = sv->Mp;
+  double* W = sv->kmm->W;
+  const Run ra{sv->kmm, sv->kmm->d_active, 1, sa};
+  factor_u(sv, sa);
+  gemm(ra, gemm_args(sv->dR, Mp, sv->dR, Mp, sv->Sm1, Mp, 0, Mp, Mp, Mp, TRI_KMAX_I | TRI_KMAX_J, 0,
+                     1.0, 0.0), EPI_STORE, false, true);
+  launch_diag_add(sv->Sm1, Mp, M, -1.0, sa);
+  gemm(ra, gemm_args(sv->Sm1, Mp, W, Mp, sv->T, Mp, 0, Mp, Mp, Mp, TRI_KMIN_J, 0, 1.0, 0.0), EPI_STORE,
+       false, false);
+  gemm(ra, gemm_args(W, Mp, sv->T, Mp, sv->P, Mp, 0, Mp, Mp, Mp, TRI_KMIN_I, 0, 1.0, 0.0), EPI_STORE,
+       true, false);
+}
+
+// K̄mn = u g_μᵀ + Y contracted with ∂Kmn/∂θ, ∂Kmn/∂Z (θ sums added to what part holds); w = Kmn g_μ
+int rows_pass(gpx_svgp* sv, hipStream_t s) {
+  gpx_ctx* ctx = sv->ctx;
+  const int M = sv->M, Mp = sv->Mp, Nc = sv->Ncols, D = sv->D;
+  RowsArgs ro{};
+  ro.Zr = sv->dZ; ro.Xc = sv->X; ro.D = D; ro.nrows = M; ro.ncols = sv->N; ro.Y = sv->Ybuf; ro.ldy = Nc;
+  ro.sym = 0; ro.u = sv->u; ro.g = sv->g; ro.zscale = 1.0; ro.spec = sv->kmm->d_specs;
+  ro.theta = sv->d_theta; ro.chunk = sv->rows_chunk; ro.Mp = Mp;
+  int rc = rows_alloc(sv, ro);
+  if (rc != GPX_OK) return rc;
+  ro.part_theta = sv->pth; ro.part_z = sv->pz; ro.part_w = sv->pw;
+  HIPX(ctx, hipMemsetAsync(sv->pz, 0, sizeof(double) * rows_chunks(ro) * Mp * D, s));
+  HIPX(ctx, hipMemsetAsync(sv->pw, 0, sizeof(double) * rows_chunks(ro) * Mp, s));
+  launch_rows(ro, single_term(sv), s);
+  sum_into(sv->pth, GPX_THETA_STRIDE, rows_blocks(ro), GPX_THETA_STRIDE, sv->part + sv->off_th, 1, s);
+  sum_into(sv->pz, (long long)Mp * D, rows_chunks(ro), (long long)Mp * D, sv->part + sv->off_z, 0, s);
+  sum_into(sv->pw, Mp, rows_chunks(ro), Mp, sv->part + sv->off_w, 0, s);
+  return GPX_OK;
+}
+
 int check_info(gpx_svgp* sv, int32_t* info, hipStream_t s) {
   gpx_ctx* ctx = sv->ctx;
   HIPX(ctx, hipMemcpyAsync(&sv->h_info, sv->kmm->d_info, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -127,6 +194,74 @@ int check_info(gpx_svgp* sv, int32_t* info, hipStream_t s) {
   return GPX_OK;
 }
 
+// eval_local of a per-point object after prelude(): the launch sequence of the header comment.
+int eval_local_per_point(gpx_svgp* sv, const double* theta, int32_t* info, hipStream_t s) {
+  gpx_ctx* ctx = sv->ctx;
+  const int Mp = sv->Mp, Nc = sv->Ncols;
+  const double scale = sv->num_data / (double)sv->n_total;
+  const Run r{sv->kmm, sv->kmm->d_active, 1, s};
+  hipStream_t sa = sv->kmm->aux[0];
+  hipEvent_t e_up = sv->kmm->ev[kEvents - 2], e_m = sv->kmm->ev[kEvents - 1];
+  HIPX(ctx, hipEventRecord(e_up, s));
+  build_kmn(sv, s);
+  // the M×M chain on the auxiliary stream, as on the closed-form route
+  HIPX(ctx, hipStreamWaitEvent(sa, e_up, 0));
+  mm_chain(sv, sa);
+  HIPX(ctx, hipEventRecord(e_m, sa));
+  HIPX(ctx, hipStreamWaitEvent(s, e_m, 0));
+  // Q = P Kmn (in Ybuf),  μ = Kmnᵀ u
+  gemm(r, gemm_args(sv->P, Mp, sv->Kmn, Nc, sv->Ybuf, Nc, 0, Mp, Nc, Mp, 0, 0, 1.0, 0.0), EPI_STORE,
+       false, false);
+  TrmvArgs t{};
+  t.active = sv->kmm->d_active; t.Wm = sv->Kmn; t.sW = 0; t.ld = Nc; t.x = sv->u; t.sx = 0;
+  t.nvalid = nullptr; t.y = sv->mu; t.sy = 0; t.rows = Mp; t.cols = Nc; t.lower = 0;
+  launch_trmv_t(t, 1, s);
+  // v_n = k_nn + Σ_m Kmn[m,n] Q[m,n]
+  SvgpColvarArgs cv{};
+  cv.Kmn = sv->Kmn; cv.Q = sv->Ybuf; cv.ld = Nc; cv.rows = Mp; cv.slices = sv->slices;
+  cv.X = sv->X; cv.D = sv->D; cv.n = sv->N; cv.spec = sv->kmm->d_specs; cv.theta = sv->d_theta;
+  cv.part = sv->vpart;
+  launch_svgp_colvar(cv, s);
+  sum_into(sv->vpart, Nc, sv->slices, Nc, sv->v, 0, s);
+  // E, ∂E/∂φ and the row weights g_μ, g_v (already times s; zero on the padding columns)
+  SvgpLikQuadArgs qa{};
+  qa.q.mu = sv->mu; qa.q.v = sv->v; qa.q.y = sv->Y; qa.q.n = sv->N; qa.q.npad = Nc; qa.q.lik = sv->lik;
+  qa.q.phi = theta[sv->spec.n_params]; qa.q.df = sv->df; qa.q.c0 = sv->c0; qa.q.gmu = sv->g; qa.q.gv = sv->gv;
+  qa.q.part = sv->pq; qa.scale = scale;
+  launch_svgp_lik_quad(qa, s);
+  sum_into(sv->pq, 2, svgp_lik_quad_blocks(Nc), 2, sv->part + sv->off_sc, 0, s);
+  HIPX(ctx, hipMemcpyAsync(sv->part + sv->off_sc + 2, &sv->h_nloc, sizeof(double), hipMemcpyHostToDevice, s));
+  // Y = 2 Q diag(g_v) in place,  Ks = Kmn diag(g_v)
+  SvgpColscaleArgs cs{};
+  cs.Kmn = sv->Kmn; cs.Y = sv->Ybuf; cs.Ks = sv->Ks; cs.ld = Nc; cs.rows = Mp; cs.gv = sv->gv;
+  launch_svgp_colscale(cs, s);
+  // G_w = Ks Kmnᵀ (lower; symmetric), split-K over the nc column chunks, then summed
+  {
+    const Run rk{sv->kmm, sv->d_iota, sv->nc, s};
+    GemmArgs gg = gemm_args(sv->Ks, Nc, sv->Kmn, Nc, sv->Gpart, Mp, 0, Mp, Mp, sv->chunkK, 0, 1, 1.0, 0.0);
+    gg.sA = sv->chunkK; gg.sB = sv->chunkK; gg.sC = (long long)Mp * Mp;
+    gemm(rk, gg, EPI_STORE, false, true);
+    sum_into(sv->Gpart, (long long)Mp * Mp, sv->nc, (long long)Mp * Mp, sv->part + sv->off_G, 0, s);
+  }
+  // Σ_n g_v,n ∂k_nn/∂θ
+  SvgpKnnArgs ka{};
+  ka.X = sv->X; ka.D = sv->D; ka.n = sv->N; ka.gv = sv->gv; ka.spec = sv->kmm->d_specs;
+  ka.theta = sv->d_theta; ka.part = sv->pknn;
+  launch_svgp_knn(ka, s);
+  sum_into(sv->pknn, GPX_THETA_STRIDE, svgp_lik_knn_blocks(sv->N), GPX_THETA_STRIDE, sv->part + sv->off_th, 0, s);
+  int rc = rows_pass(sv, s);
+  if (rc != GPX_OK) return rc;
+  HIPX(ctx, hipGetLastError());
+  rc = check_info(sv, info, s);
+  if (rc != GPX_OK) return rc;
+  sv->local_done = true;
+  return GPX_OK;
+}
+
+int create_impl(gpx_ctx* ctx, int N, int M, int D, const double* X, const double* Y,
+                const gpx_kernel_spec* spec, double num_data, long long n_total, bool per_point,
+                int likelihood, double df, gpx_svgp** out);
+
 }  // namespace
 
 extern "C" {
@@ -134,6 +269,28 @@ extern "C" {
 int gpx_svgp_create(gpx_ctx* ctx, int N, int M, int D, const double* X, const double* Y,
                     const gpx_kernel_spec* spec, double num_data, long long n_total,
                     gpx_svgp** out) {
+  return create_impl(ctx, N, M, D, X, Y, spec, num_data, n_total, false, GPX_LIK_GAUSSIAN, 3.0, out);
+}
+
+int gpx_svgp_create_lik(gpx_ctx* ctx, int N, int M, int D, const double* X, const double* Y,
+                        const gpx_kernel_spec* spec, double num_data, long long n_total,
+                        int likelihood, double df, gpx_svgp** out) {
+  if (!ctx || !out) return GPX_BAD_ARG;
+  *out = nullptr;
+  if (likelihood != GPX_LIK_GAUSSIAN && likelihood != GPX_LIK_STUDENT_T)
+    return fail(ctx, GPX_BAD_ARG, "unknown svgp likelihood");
+  if (likelihood == GPX_LIK_STUDENT_T && (!(df > 0.0) || !std::isfinite(df)))
+    return fail(ctx, GPX_BAD_ARG, "StudentT df must be finite and > 0");
+  return create_impl(ctx, N, M, D, X, Y, spec, num_data, n_total, true, likelihood, df, out);
+}
+
+}  // extern "C"
+
+namespace {
+
+int create_impl(gpx_ctx* ctx, int N, int M, int D, const double* X, const double* Y,
+                const gpx_kernel_spec* spec, double num_data, long long n_total, bool per_point,
+                int likelihood, double df, gpx_svgp** out) {
   if (!ctx || !out) return GPX_BAD_ARG;
   *out = nullptr;
   if (N < 1 || M < 1 || D < 1 || D > GPX_MAX_DIM || !X || !Y || !spec || !(num_data > 0.0) ||
@@ -215,9 +372,29 @@ int gpx_svgp_create(gpx_ctx* ctx, int N, int M, int D, const double* X, const do
   if (hipMemcpy(sv->d_iota, iota.data(), sizeof(int) * sv->nc, hipMemcpyHostToDevice) != hipSuccess)
     return bail("upload failed");
   sv->h_nloc = (double)N;
+  if (per_point) {
+    sv->per_point = true;
+    sv->lik = likelihood;
+    sv->df = df;
+    sv->c0 = likelihood == GPX_LIK_GAUSSIAN
+                 ? -0.5 * std::log(2.0 * M_PI)
+                 : std::lgamma(0.5 * (df + 1.0)) - std::lgamma(0.5 * df) - 0.5 * (std::log(df) + std::log(M_PI));
+    sv->slices = svgp_colvar_slices(Mp, sv->Ncols);
+    if (hipMalloc(&sv->Ks, sizeof(double) * mn) != hipSuccess ||
+        hipMalloc(&sv->v, sizeof(double) * sv->Ncols) != hipSuccess ||
+        hipMalloc(&sv->gv, sizeof(double) * sv->Ncols) != hipSuccess ||
+        hipMalloc(&sv->vpart, sizeof(double) * sv->slices * sv->Ncols) != hipSuccess ||
+        hipMalloc(&sv->pq, sizeof(double) * svgp_lik_quad_blocks(sv->Ncols) * 2) != hipSuccess ||
+        hipMalloc(&sv->pknn, sizeof(double) * svgp_lik_knn_blocks(N) * GPX_THETA_STRIDE) != hipSuccess)
+      return bail("out of device memory for the per-point workspace");
+  }
   *out = sv;
   return GPX_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 int gpx_svgp_destroy(gpx_svgp* sv) {
   if (!sv) return GPX_BAD_ARG;
@@ -231,7 +408,8 @@ int gpx_svgp_destroy(gpx_svgp* sv) {
                   (void*)sv->ahat, (void*)sv->Rbar, (void*)sv->Kmn, (void*)sv->Ybuf, (void*)sv->Gpart,
                   (void*)(sv->own_part ? sv->part : nullptr), (void*)sv->pth, (void*)sv->pz, (void*)sv->pw, (void*)sv->pres,
                   (void*)sv->ptr, (void*)sv->fin, (void*)sv->d_iota, (void*)sv->Kms, (void*)sv->V,
-                  (void*)sv->pA, (void*)sv->pB})
+                  (void*)sv->pA, (void*)sv->pB, (void*)sv->Ks, (void*)sv->v, (void*)sv->gv, (void*)sv->vpart,
+                  (void*)sv->pq, (void*)sv->pknn})
     if (p) (void)hipFree(p);
   delete sv;
   return GPX_OK;
@@ -263,22 +441,16 @@ int gpx_svgp_eval_local(gpx_svgp* sv, const double* theta, const double* Z, cons
   sv->local_done = false;
   int rc = prelude(sv, theta, Z, q_mu, q_sqrt, s);
   if (rc != GPX_OK) return rc;
-  const int M = sv->M, Mp = sv->Mp, Nc = sv->Ncols, D = sv->D;
+  if (sv->per_point) return eval_local_per_point(sv, theta, info, s);
+  const int Mp = sv->Mp, Nc = sv->Ncols, D = sv->D;
   const double s2 = theta[sv->spec.n_params];
   const double scale = sv->num_data / (double)sv->n_total;
   const double c2 = -scale / s2;  // 2c
   const Run r{sv->kmm, sv->kmm->d_active, 1, s};
-  double* W = sv->kmm->W;
   hipStream_t sa = sv->kmm->aux[0];
   hipEvent_t e_up = sv->kmm->ev[kEvents - 2], e_m = sv->kmm->ev[kEvents - 1];
   HIPX(ctx, hipEventRecord(e_up, s));
-  // Kmn = k(Z, X) (rows ≥ M and columns ≥ N are zero)
-  BuildArgs ba{};
-  ba.active = sv->kmm->d_active; ba.specs = sv->kmm->d_specs; ba.theta = sv->d_theta;
-  ba.nvalid = sv->kmm->d_n; ba.X = sv->dZ; ba.sX = 0; ba.X2 = sv->X; ba.sX2 = 0; ba.D = D;
-  ba.m2 = sv->N; ba.out = sv->Kmn; ba.sOut = 0; ba.ldo = Nc; ba.rows = Mp; ba.cols = Nc;
-  ba.symmetric = 0; ba.rows_valid = 0;
-  launch_build(ba, 1, s);
+  build_kmn(sv, s);
   // G = Kmn Kmnᵀ (lower), split-K over nc column chunks, then summed
   {
     const Run rk{sv->kmm, sv->d_iota, sv->nc, s};
@@ -291,19 +463,8 @@ int gpx_svgp_eval_local(gpx_svgp* sv, const double* theta, const double* Z, cons
   // auxiliary stream while the main stream builds Kmn and runs the split-K SYRK for G
   // (enqueued first, so the chain's many small launches do not delay the big ones).
   HIPX(ctx, hipStreamWaitEvent(sa, e_up, 0));
-  {
-    const Run ra{sv->kmm, sv->kmm->d_active, 1, sa};
-    factor_u(sv, sa);
-    // S − I = q_sqrt q_sqrtᵀ − I;  P = Wᵀ (S − I) W
-    gemm(ra, gemm_args(sv->dR, Mp, sv->dR, Mp, sv->Sm1, Mp, 0, Mp, Mp, Mp, TRI_KMAX_I | TRI_KMAX_J, 0,
-                       1.0, 0.0), EPI_STORE, false, true);
-    launch_diag_add(sv->Sm1, Mp, M, -1.0, sa);
-    gemm(ra, gemm_args(sv->Sm1, Mp, W, Mp, sv->T, Mp, 0, Mp, Mp, Mp, TRI_KMIN_J, 0, 1.0, 0.0), EPI_STORE,
-         false, false);
-    gemm(ra, gemm_args(W, Mp, sv->T, Mp, sv->P, Mp, 0, Mp, Mp, Mp, TRI_KMIN_I, 0, 1.0, 0.0), EPI_STORE,
-         true, false);
-    HIPX(ctx, hipEventRecord(e_m, sa));
-  }
+  mm_chain(sv, sa);
+  HIPX(ctx, hipEventRecord(e_m, sa));
   HIPX(ctx, hipStreamWaitEvent(s, e_m, 0));
   // μ = Kmnᵀ u
   TrmvArgs t{};
@@ -322,20 +483,8 @@ int gpx_svgp_eval_local(gpx_svgp* sv, const double* theta, const double* Z, cons
   // Y = 2c P Kmn
   gemm(r, gemm_args(sv->P, Mp, sv->Kmn, Nc, sv->Ybuf, Nc, 0, Mp, Nc, Mp, 0, 0, c2, 0.0), EPI_STORE,
        false, false);
-  // K̄mn = u g_μᵀ + Y contracted with ∂Kmn/∂θ, ∂Kmn/∂Z; w = Kmn g_μ
-  RowsArgs ro{};
-  ro.Zr = sv->dZ; ro.Xc = sv->X; ro.D = D; ro.nrows = M; ro.ncols = sv->N; ro.Y = sv->Ybuf; ro.ldy = Nc;
-  ro.sym = 0; ro.u = sv->u; ro.g = sv->g; ro.zscale = 1.0; ro.spec = sv->kmm->d_specs;
-  ro.theta = sv->d_theta; ro.chunk = sv->rows_chunk; ro.Mp = Mp;
-  rc = rows_alloc(sv, ro);
+  rc = rows_pass(sv, s);
   if (rc != GPX_OK) return rc;
-  ro.part_theta = sv->pth; ro.part_z = sv->pz; ro.part_w = sv->pw;
-  HIPX(ctx, hipMemsetAsync(sv->pz, 0, sizeof(double) * rows_chunks(ro) * Mp * D, s));
-  HIPX(ctx, hipMemsetAsync(sv->pw, 0, sizeof(double) * rows_chunks(ro) * Mp, s));
-  launch_rows(ro, single_term(sv), s);
-  sum_into(sv->pth, GPX_THETA_STRIDE, rows_blocks(ro), GPX_THETA_STRIDE, sv->part + sv->off_th, 1, s);
-  sum_into(sv->pz, (long long)Mp * D, rows_chunks(ro), (long long)Mp * D, sv->part + sv->off_z, 0, s);
-  sum_into(sv->pw, Mp, rows_chunks(ro), Mp, sv->part + sv->off_w, 0, s);
   HIPX(ctx, hipGetLastError());
   rc = check_info(sv, info, s);
   if (rc != GPX_OK) return rc;
@@ -354,7 +503,7 @@ int gpx_svgp_eval_finish(gpx_svgp* sv, double* elbo, double* grad_theta, double*
   const int M = sv->M, Mp = sv->Mp, D = sv->D, np = sv->spec.n_params;
   const double s2 = sv->h_theta[np];
   const double scale = sv->num_data / (double)sv->n_total;
-  const double c2 = -scale / s2;
+  const double c2 = sv->per_point ? 2.0 : -scale / s2;  // per-point route: the weights are inside G_w
   const Run r{sv->kmm, sv->kmm->d_active, 1, s};
   double* W = sv->kmm->W;
   double* G = sv->part + sv->off_G;
@@ -424,9 +573,14 @@ int gpx_svgp_eval_finish(gpx_svgp* sv, double* elbo, double* grad_theta, double*
     kl -= std::log(sv->h_R[(size_t)i * Mp + i] * sv->h_R[(size_t)i * Mp + i]);
   }
   kl *= 0.5;
-  *elbo = scale * (-0.5 * ntot * std::log(2.0 * M_PI * s2) - (sc[0] + sumv) / (2.0 * s2)) - kl;
   for (int p = 0; p < GPX_THETA_STRIDE; ++p) grad_theta[p] = (p < np) ? pth[p] + fth[p] : 0.0;
-  grad_theta[np] = scale * (-0.5 * ntot / s2 + 0.5 * (sc[0] + sumv) / (s2 * s2));
+  if (sv->per_point) {  // sc: Σ ve, Σ ∂ve/∂φ over all shards
+    *elbo = scale * sc[0] - kl;
+    grad_theta[np] = scale * sc[1];
+  } else {
+    *elbo = scale * (-0.5 * ntot * std::log(2.0 * M_PI * s2) - (sc[0] + sumv) / (2.0 * s2)) - kl;
+    grad_theta[np] = scale * (-0.5 * ntot / s2 + 0.5 * (sc[0] + sumv) / (s2 * s2));
+  }
   for (int m = 0; m < M; ++m)
     for (int d = 0; d < D; ++d) grad_Z[(size_t)m * D + d] = pz[(size_t)m * D + d] + fz[(size_t)m * D + d];
   for (int m = 0; m < M; ++m) grad_qmu[m] = sv->h_ahat[m] - sv->h_q[m];
@@ -456,11 +610,22 @@ int gpx_svgp_predict(gpx_svgp* sv, const double* theta, const double* Z, const d
   if (!Xnew || Mn < 1 || !mean || !var) return fail(ctx, GPX_BAD_ARG, "bad predict args");
   if (((long long)Mn + 63) / 64 * 64 > kGemmMaxLd)
     return fail(ctx, GPX_BAD_ARG, "too many prediction points for one call (kGemmMaxLd): split Xnew");
+  const bool student = sv->per_point && sv->lik == GPX_LIK_STUDENT_T;
+  if (add_noise && student && !(sv->df > 2.0))
+    return fail(ctx, GPX_BAD_ARG, "StudentT predict_y needs df > 2 (the variance is scale² df/(df − 2))");
   HIPX(ctx, hipSetDevice(ctx->device));
   hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
   sv->local_done = false;
   int rc = prelude(sv, theta, Z, q_mu, q_sqrt, s);
   if (rc != GPX_OK) return rc;
+  if (add_noise && student) {
+    // the variance predict_y adds, in the θ row's noise slot (svgp_predvar_kernel reads it there)
+    const int np = sv->spec.n_params;
+    sv->h_thdev = sv->h_theta;
+    sv->h_thdev[np] = theta[np] * theta[np] * sv->df / (sv->df - 2.0);
+    HIPX(ctx, hipMemcpyAsync(sv->d_theta, sv->h_thdev.data(), sizeof(double) * GPX_THETA_STRIDE,
+                             hipMemcpyHostToDevice, s));
+  }
   factor_u(sv, s);
   const int Mp = sv->Mp, D = sv->D;
   const int Mnp = (Mn + 63) / 64 * 64;

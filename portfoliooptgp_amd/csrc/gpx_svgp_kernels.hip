@@ -5,47 +5,14 @@
 // O(M²) elementwise tail. All HBM streams are coalesced along the N (data) axis.
 #include <hip/hip_runtime.h>
 #include "gpx_internal.h"
+#include "gpx_reduce.h"
 
 namespace gpx {
 
 namespace {
 
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 constexpr int kRowsPerBlock = 16;   // 4 waves x 4 rows
 constexpr int kRowsLds = 4096;      // doubles of column points staged per block
-
-__device__ int theta_slot(const DevSpec* gs, int p) {
-  // θ index p -> (term, q) slot t*3+q of the per-term derivative sums, or -1
-  for (int t = 0; t < gs->n_terms; ++t) {
-    const int o = gs->terms[t].param_offset, kind = gs->terms[t].kind;
-    const int np = (kind == GPX_RQ || kind == GPX_PERIODIC_SE) ? 3 : (kind == GPX_LINEAR ? 1 : 2);
-    if (p >= o && p < o + np) return t * 3 + (p - o);
-  }
-  return -1;
-}
-
-// Block reduction of the per-lane sums[4][3] into out[16] (θ layout).
-template <int NT>
-__device__ void reduce_theta(double (&sums)[NT][3], const DevSpec* gs, double* sred, double* out) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int t = 0; t < GPX_MAX_TERMS; ++t)
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const double v = t < NT ? wsum(sums[t < NT ? t : 0][q]) : 0.0;
-      if (lane == 0) sred[wave * 16 + t * 3 + q] = v;
-    }
-  __syncthreads();
-  if (threadIdx.x < GPX_THETA_STRIDE) {
-    const int slot = theta_slot(gs, threadIdx.x);
-    out[threadIdx.x] = slot >= 0 ? sred[slot] + sred[16 + slot] + sred[32 + slot] + sred[48 + slot] : 0.0;
-  }
-}
 
 template <int DM, int NT>
 __global__ __launch_bounds__(256) void rows_kernel(RowsArgs a) {

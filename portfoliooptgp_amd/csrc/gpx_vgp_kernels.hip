@@ -4,6 +4,7 @@
 // likelihood, 20-point Gauss–Hermite for Student-t) and the N×N elementwise tail.
 #include <hip/hip_runtime.h>
 #include "gpx_internal.h"
+#include "gpx_quad.h"
 
 namespace gpx {
 
@@ -14,22 +15,6 @@ __device__ __forceinline__ double wsum(double v) {
   for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
-
-// numpy.polynomial.hermite.hermgauss(20): nodes x_i and weights w_i (GPflow's NDiagGHQuadrature
-// divides the weights by √π and evaluates at μ + √(2v) x_i)
-__constant__ double kGhX[kGhPoints] = {
-    -5.3874808900112328, -4.6036824495507442, -3.9447640401156252, -3.3478545673832163,
-    -2.7888060584281305, -2.2549740020892757, -1.7385377121165861, -1.2340762153953231,
-    -0.73747372854539439, -0.24534070830090124, 0.24534070830090124, 0.73747372854539439,
-    1.2340762153953231, 1.7385377121165861, 2.2549740020892757, 2.7888060584281305,
-    3.3478545673832163, 3.9447640401156252, 4.6036824495507442, 5.3874808900112328};
-__constant__ double kGhW[kGhPoints] = {
-    2.2293936455341447e-13, 4.3993409922731747e-10, 1.0860693707692782e-07, 7.8025564785320599e-06,
-    0.00022833863601635365, 0.0032437733422378567, 0.024810520887463643, 0.10901720602002329,
-    0.28667550536283415, 0.46224366960061009, 0.46224366960061009, 0.28667550536283415,
-    0.10901720602002329, 0.024810520887463643, 0.0032437733422378567, 0.00022833863601635365,
-    7.8025564785320599e-06, 1.0860693707692782e-07, 4.3993409922731747e-10, 2.2293936455341447e-13};
-constexpr double kInvSqrtPi = 0.56418958354775628;  // 1/√π
 
 // L = tril(P) on the leading n×n block (P = K̃ Wᵀ from the GEMM), zeros above the diagonal, the
 // identity on the padding: every np×np entry is written.
@@ -78,33 +63,7 @@ __global__ __launch_bounds__(256) void vgp_quad_kernel(VgpQuadArgs a) {
   if (n < a.n) {
     const double mu = a.mu[n], v = a.v[n], y = a.y[n];
     double gm, gv;
-    if (a.lik == GPX_LIK_GAUSSIAN) {
-      const double s = a.phi, r = y - mu, q = fma(r, r, v);
-      E = a.c0 - 0.5 * log(s) - q / (2.0 * s);
-      gm = r / s;
-      gv = -0.5 / s;
-      gphi = -0.5 / s + q / (2.0 * s * s);
-    } else {
-      const double sc = a.phi, df = a.df, sd = sqrt(2.0 * v), isd = 1.0 / sd;
-      const double s2df = sc * sc * df, lsc = log(sc);
-      gm = 0.0;
-      gv = 0.0;
-#pragma unroll 4
-      for (int i = 0; i < kGhPoints; ++i) {
-        const double w = kGhW[i] * kInvSqrtPi, x = kGhX[i];
-        const double d = y - fma(sd, x, mu);        // y − f
-        const double d2 = d * d;
-        const double den = s2df + d2;                // scale² df + (y − f)²
-        const double lp = a.c0 - lsc - 0.5 * (df + 1.0) * log1p(d2 / s2df);
-        const double dlf = (df + 1.0) * d / den;     // ∂logp/∂f
-        const double dls = (-1.0 + (df + 1.0) * d2 / den) / sc;  // ∂logp/∂scale
-        E = fma(w, lp, E);
-        gm = fma(w, dlf, gm);
-        gv = fma(w * x, dlf, gv);
-        gphi = fma(w, dls, gphi);
-      }
-      gv *= isd;
-    }
+    ve_row(a.lik, a.phi, a.df, a.c0, mu, v, y, E, gm, gv, gphi);
     a.gmu[n] = gm;
     a.gv[n] = gv;
   } else if (n < a.npad) {

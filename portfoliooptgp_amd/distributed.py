@@ -412,7 +412,8 @@ def fit_svgp_sharded(model, X_local, Y_local, n_total: int, group=None, engine=N
     """Fit ``model`` (models.SVGP) on data sharded by rows over the ranks of ``group``: every
     rank runs the same scipy L-BFGS-B on the all-reduced (hence identical) ELBO gradient, so
     the replicated variational parameters stay bit-identical across ranks. ``engine`` may be
-    injected (tests); by default an SVGPEngine on this rank's rows with n_total set."""
+    injected (tests); by default an SVGPEngine on this rank's rows with n_total set and the
+    model's likelihood and route (Gaussian, or ``per_point=True`` with Gaussian or StudentT)."""
     from .engine import SVGPEngine
     from .kernels import compile_spec
     from .optimizers import Scipy
@@ -421,7 +422,7 @@ def fit_svgp_sharded(model, X_local, Y_local, n_total: int, group=None, engine=N
         D = 1 if Xl.ndim == 1 else int(Xl.shape[1])
         engine = SVGPEngine(X_local, Y_local, compile_spec(model.kernel, D), model.M,
                             num_data=float(model.num_data if model.num_data is not None else n_total),
-                            n_total=n_total, device=model.device)
+                            n_total=n_total, device=model.device, **model._engine_likelihood())
 
     def loss_and_grad(variables=None):
         variables = model.trainable_variables if variables is None else variables

@@ -638,10 +638,20 @@ class Engine:
 class SVGPEngine:
     """Device state of one SVGP data shard (include/gpx.h gpx_svgp): X [N, D] / Y [N]
     resident in HBM, Kmn / workspace owned by the library, and the per-shard partial-sum
-    buffer as a torch tensor (so torch.distributed can all-reduce it in place)."""
+    buffer as a torch tensor (so torch.distributed can all-reduce it in place).
+
+    ``likelihood`` is a GPX_LIK_* code. Gaussian objects come from gpx_svgp_create (the closed-form
+    path); StudentT ones, and Gaussian ones asked for with ``per_point=True``, from
+    gpx_svgp_create_lik (the per-point route: θ's noise slot carries the scale / the variance)."""
 
     def __init__(self, X, Y, spec: N.GpxKernelSpec, M: int, num_data: float,
-                 n_total: Optional[int] = None, device: Optional[int] = None):
+                 n_total: Optional[int] = None, device: Optional[int] = None,
+                 likelihood: int = N.GPX_LIK_GAUSSIAN, df: float = 3.0, per_point: bool = False):
+        if likelihood not in (N.GPX_LIK_GAUSSIAN, N.GPX_LIK_STUDENT_T):
+            raise ValueError(f"unknown likelihood code {likelihood}")
+        self.likelihood = int(likelihood)
+        self.df = float(df)
+        self.per_point = bool(per_point) or self.likelihood != N.GPX_LIK_GAUSSIAN
         self.device = require_gpu(device)
         self.ctx = N.Context.get(self.device)
         self.lib = self.ctx.lib
@@ -658,11 +668,20 @@ class SVGPEngine:
         self.spec = spec
         torch.cuda.synchronize(self.device)
         h = ctypes.c_void_p()
-        rc = self.lib.gpx_svgp_create(self.ctx.handle, self.N, self.M, self.D,
-                                      ctypes.c_void_p(self.X.data_ptr()), ctypes.c_void_p(self.Y.data_ptr()),
-                                      ctypes.byref(self.spec), float(num_data), self.n_total, ctypes.byref(h))
+        if self.per_point:
+            what = "gpx_svgp_create_lik"
+            rc = self.lib.gpx_svgp_create_lik(self.ctx.handle, self.N, self.M, self.D,
+                                              ctypes.c_void_p(self.X.data_ptr()),
+                                              ctypes.c_void_p(self.Y.data_ptr()), ctypes.byref(self.spec),
+                                              float(num_data), self.n_total, self.likelihood, self.df,
+                                              ctypes.byref(h))
+        else:
+            what = "gpx_svgp_create"
+            rc = self.lib.gpx_svgp_create(self.ctx.handle, self.N, self.M, self.D,
+                                          ctypes.c_void_p(self.X.data_ptr()), ctypes.c_void_p(self.Y.data_ptr()),
+                                          ctypes.byref(self.spec), float(num_data), self.n_total, ctypes.byref(h))
         if rc != N.GPX_OK:
-            raise N.GPXError(f"gpx_svgp_create failed ({rc}): {self.ctx.last_error()}")
+            raise N.GPXError(f"{what} failed ({rc}): {self.ctx.last_error()}")
         self.handle = h
         ptr, ln = ctypes.c_void_p(), ctypes.c_longlong()
         self.lib.gpx_svgp_partials(h, ctypes.byref(ptr), ctypes.byref(ln))

@@ -1,6 +1,7 @@
 """gpflow.likelihoods.Gaussian: variance σn² with a 1e-6 lower bound
 (``Gaussian(variance=1.0, variance_lower_bound=1e-6)``), and gpflow.likelihoods.StudentT
-(``StudentT(scale=1.0, df=3.0)``: a positive scale parameter, a fixed df), which models.VGP takes."""
+(``StudentT(scale=1.0, df=3.0)``: a positive scale parameter, a fixed df), which models.VGP takes, and
+models.SVGP with ``per_point=True``."""
 from __future__ import annotations
 
 from .parameter import Parameter

@@ -294,8 +294,8 @@ def predict_f_batch(models: Sequence[GPR], Xnews: Sequence, add_noise: bool = Fa
 
 
 class SVGP:
-    """gpflow.models.SVGP with a Gaussian likelihood and GPflow's defaults (whiten=True, full
-    q_sqrt, zero mean, one latent GP) — the cells at test_scripts/SVGP.py:461-478 and
+    """gpflow.models.SVGP with a Gaussian or StudentT likelihood and GPflow's defaults (whiten=True,
+    full q_sqrt, zero mean, one latent GP) — the cells at test_scripts/SVGP.py:461-478 and
     test_scripts/GPR.py:118-138::
 
         m = SVGP(kernel=k, likelihood=Gaussian(variance=1e-4), inducing_variable=Z, num_data=N)
@@ -305,20 +305,35 @@ class SVGP:
         mean, var = m.predict_f(X_test)
 
     ELBO, gradients and predictions come from libgpx.so (gpx_svgp_*); trainable variables
-    are ordered as tf.Module flattens SVGP: inducing_variable.Z, kernel.*, likelihood.variance,
-    q_mu, q_sqrt (FillTriangular-unconstrained)."""
+    are ordered as tf.Module flattens SVGP: inducing_variable.Z, kernel.*, likelihood.variance
+    (likelihood.scale for StudentT), q_mu, q_sqrt (FillTriangular-unconstrained).
 
-    def __init__(self, kernel: Kernel, likelihood: Gaussian, inducing_variable, *, mean_function=None,
+    ``per_point=True`` selects the per-point evaluation route (gpx_svgp_create_lik): the marginal of
+    every data row and GPflow's variational expectation of it, for either likelihood. It is what
+    serves ``likelihoods.StudentT(scale, df)`` (20-point Gauss–Hermite; predict_y adds
+    scale²·df/(df − 2)), and it is opt-in::
+
+        m = SVGP(kernel=k, likelihood=StudentT(), inducing_variable=Z, num_data=N, per_point=True)
+
+    Without the keyword the model is what it was: the Gaussian likelihood by the closed-form route,
+    and StudentT refused at construction (one more M×N device buffer and about a tenth more time
+    per evaluation are not taken without being asked for)."""
+
+    def __init__(self, kernel: Kernel, likelihood, inducing_variable, *, mean_function=None,
                  num_latent_gps: int = 1, q_diag: bool = False, q_mu=None, q_sqrt=None,
-                 whiten: bool = True, num_data: Optional[int] = None, device: Optional[int] = None):
+                 whiten: bool = True, num_data: Optional[int] = None, device: Optional[int] = None,
+                 per_point: bool = False):
         from .inducing_variables import InducingPoints
         from .parameter import ArrayParameter
         if mean_function is not None:
             raise NotImplementedError("only the zero mean function (GPflow default) is supported")
         if num_latent_gps != 1 or q_diag or not whiten:
             raise NotImplementedError("SVGP supports GPflow's defaults: one latent GP, full q_sqrt, whiten=True")
-        if not isinstance(likelihood, Gaussian):
-            raise NotImplementedError("SVGP supports the Gaussian likelihood")
+        if not isinstance(likelihood, (Gaussian, StudentT)):
+            raise NotImplementedError("SVGP supports the Gaussian and StudentT likelihoods")
+        if isinstance(likelihood, StudentT) and not per_point:
+            raise NotImplementedError("SVGP evaluates the StudentT likelihood by the per-point route only: pass "
+                                      "per_point=True (the Gaussian and StudentT likelihoods are supported)")
         _refuse_ard(kernel, "SVGP")
         self.kernel = kernel
         self.likelihood = likelihood
@@ -328,6 +343,7 @@ class SVGP:
         self.num_data = num_data
         self.num_latent_gps = 1
         self.whiten = True
+        self.per_point = bool(per_point)
         self.q_mu = ArrayParameter(np.zeros((M, 1)) if q_mu is None else np.asarray(q_mu).reshape(M, 1),
                                    name="q_mu")
         self.q_sqrt = ArrayParameter(np.eye(M)[None] if q_sqrt is None else q_sqrt,
@@ -349,10 +365,20 @@ class SVGP:
     def trainable_variables(self):
         return tuple(p.unconstrained_variable for p in self.trainable_parameters)
 
+    @property
+    def _lik_param(self) -> Parameter:
+        return self.likelihood.scale if isinstance(self.likelihood, StudentT) else self.likelihood.variance
+
+    def _engine_likelihood(self) -> dict:
+        """The likelihood arguments of the SVGPEngine that serves this model."""
+        if isinstance(self.likelihood, StudentT):
+            return dict(likelihood=N.GPX_LIK_STUDENT_T, df=self.likelihood.df, per_point=True)
+        return dict(likelihood=N.GPX_LIK_GAUSSIAN, per_point=self.per_point)
+
     def _param_paths(self):
         return ([("SVGP.inducing_variable.Z", self.inducing_variable.Z)]
                 + [("SVGP.kernel." + n if n else "SVGP.kernel", p) for n, p in self.kernel._param_paths("")]
-                + [("SVGP.likelihood.variance", self.likelihood.variance),
+                + [("SVGP.likelihood." + self._lik_param.name, self._lik_param),
                    ("SVGP.q_mu", self.q_mu), ("SVGP.q_sqrt", self.q_sqrt)])
 
     @property
@@ -364,7 +390,7 @@ class SVGP:
         kp = self.kernel.parameters
         for i, p in enumerate(kp):
             row[i] = p.value
-        row[len(kp)] = self.likelihood.variance.value
+        row[len(kp)] = self._lik_param.value
         return row
 
     def _state(self):
@@ -388,7 +414,7 @@ class SVGP:
             D = 1 if Xa.ndim == 1 else int(Xa.shape[1])
             eng = SVGPEngine(X, Y, compile_spec(self.kernel, D), self.M,
                              num_data=float(self.num_data if self.num_data is not None else n),
-                             device=self.device)
+                             device=self.device, **self._engine_likelihood())
             hit = (eng, X, Y)
             self._engines = {key: hit}
         return hit[0]
@@ -423,7 +449,7 @@ class SVGP:
             p = v._param
             if p is self.inducing_variable.Z:
                 parts.append(-np.asarray(gZ).ravel())
-            elif p is self.likelihood.variance:
+            elif p is self._lik_param:
                 parts.append(np.array([-gth[len(kp)] * p.dtheta_du()]))
             elif id(p) in pindex:
                 parts.append(np.array([-gth[pindex[id(p)]] * p.dtheta_du()]))
