@@ -459,6 +459,48 @@ int gpx_svgp_predict(gpx_svgp* svgp, const double* theta, const double* Z, const
                      double* var, int32_t* info, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * A batch of small SVGP models, one fused launch per call: the sweep of the reference's
+ * train_svgp_model (test_scripts/GPR.py:118-138, GPR_Entropy.py:137-157, SVGP.py:459-545: per
+ * kernel one SVGP(kernel, Gaussian(1e-4), inducing_variable=X[:20]), N = 5..~800). The model and
+ * its arithmetic are gpx_svgp_create's (whitened, Gaussian likelihood by the closed form, jitter
+ * 1e-6, num_data scaling with n_total = n); each model is evaluated whole by one workgroup.
+ * Limits (gpx_svgp_small_limits; over them GPX_BAD_ARG): M <= 32, N <= 4096, D <= GPX_MAX_DIM;
+ * specs with GPX_TERM_ARD are refused as by gpx_svgp_create.
+ *
+ * An object has B slots for models of one input dimension D with n <= N_max rows and m <= M_max
+ * inducing points. gpx_svgp_small_bind copies a model's X [n, D] and Y [n] (host, fp64) into slot b.
+ * Per call, all host fp64 arrays indexed by SLOT, of which only the rows of the active slots are
+ * read / written, and of a row only the model's own leading entries (its tail is never read):
+ *   theta   [B][16]           kernel params then σn² at theta[n_params], as gpx_svgp_elbo_grad
+ *   Z       [B][M_max·D]      the slot's [m, D] inducing inputs, row-major, at the row's start
+ *   q_mu    [B][M_max]        its m entries
+ *   q_sqrt  [B][M_max·M_max]  its [m, m] row-major matrix (row stride m), lower triangle read
+ * Outputs: elbo [B]; grad_theta [B][16]; grad_Z, grad_q_mu, grad_q_sqrt in the layouts of Z, q_mu,
+ * q_sqrt (grad_q_sqrt: zeros above the diagonal); info [B]: the 1-based index of the first pivot of
+ * Kmm + 1e-6 I that is not > 0, else 0. GPX_NOT_PD when some active slot's info != 0 — that slot's
+ * outputs are then unspecified, the other slots' stay valid. theta not finite or <= 0, a non-finite
+ * Z and a zero diagonal of q_sqrt return GPX_BAD_ARG before anything is launched.
+ * A model's outputs are a function of its own inputs alone, bit for bit: they do not depend on B,
+ * on its slot, on its place in `active`, or on what else the call evaluates.
+ * gpx_svgp_small_predict: predict_f (add_noise = 0) / predict_y (1) of slot b at Xnew (HOST
+ * [Mn, D]) -> mean, var (HOST [Mn]); theta [16], Z [m, D], q_mu [m], q_sqrt [m, m] of that one model.
+ * Calls return when the outputs are filled; one object serves one thread at a time.
+ */
+typedef struct gpx_svgp_small gpx_svgp_small;
+int gpx_svgp_small_limits(int* m_max, int* n_max); /* 32, 4096; needs no device */
+int gpx_svgp_small_create(gpx_ctx* ctx, int B, int N_max, int M_max, int D, gpx_svgp_small** out);
+int gpx_svgp_small_bind(gpx_svgp_small* small, int b, int n, int m, const double* X, const double* Y,
+                        const gpx_kernel_spec* spec, double num_data);
+int gpx_svgp_small_elbo_grad(gpx_svgp_small* small, int n_active, const int32_t* active,
+                             const double* theta, const double* Z, const double* q_mu,
+                             const double* q_sqrt, double* elbo, double* grad_theta, double* grad_Z,
+                             double* grad_q_mu, double* grad_q_sqrt, int32_t* info, void* stream);
+int gpx_svgp_small_predict(gpx_svgp_small* small, int b, const double* theta, const double* Z,
+                           const double* q_mu, const double* q_sqrt, const double* Xnew, int Mn,
+                           int add_noise, double* mean, double* var, int32_t* info, void* stream);
+int gpx_svgp_small_destroy(gpx_svgp_small* small);
+
+/* ---------------------------------------------------------------------------------------
  * SGPR: gpflow.models.SGPR((X, Y), kernel, inducing_variable=Z, noise_variance=...) — the
  * collapsed (Titsias) bound of sparse GP regression with a Gaussian likelihood, zero mean, one
  * output; test_scripts/SVGP.py:395-412 (SE kernel, M = 10, N ≈ 113).

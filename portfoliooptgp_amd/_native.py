@@ -47,6 +47,8 @@ EXPORTED_SYMBOLS = (
     "gpx_batch_set_band_route",
     "gpx_svgp_create", "gpx_svgp_create_lik", "gpx_svgp_destroy", "gpx_svgp_partials", "gpx_svgp_bind_partials",
     "gpx_svgp_eval_local", "gpx_svgp_eval_finish", "gpx_svgp_elbo_grad", "gpx_svgp_predict",
+    "gpx_svgp_small_limits", "gpx_svgp_small_create", "gpx_svgp_small_bind", "gpx_svgp_small_elbo_grad",
+    "gpx_svgp_small_predict", "gpx_svgp_small_destroy",
     "gpx_sgpr_create", "gpx_sgpr_destroy", "gpx_sgpr_elbo_grad", "gpx_sgpr_predict",
     "gpx_vgp_create", "gpx_vgp_destroy", "gpx_vgp_elbo_grad", "gpx_vgp_predict",
     "gpx_host_theta_rows", "gpx_host_loss_grad_u",
@@ -233,6 +235,19 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.gpx_svgp_predict.restype = c_int
         lib.gpx_svgp_predict.argtypes = [c_void_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                          c_void_p, c_int, c_int, c_void_p, c_void_p, c_int_p, c_void_p]
+        lib.gpx_svgp_small_limits.restype = c_int
+        lib.gpx_svgp_small_limits.argtypes = [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
+        lib.gpx_svgp_small_create.restype = c_int
+        lib.gpx_svgp_small_create.argtypes = [c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p)]
+        lib.gpx_svgp_small_bind.restype = c_int
+        lib.gpx_svgp_small_bind.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, spec_p, c_double]
+        lib.gpx_svgp_small_elbo_grad.restype = c_int
+        lib.gpx_svgp_small_elbo_grad.argtypes = [c_void_p, c_int, c_int_p] + [c_void_p] * 9 + [c_int_p, c_void_p]
+        lib.gpx_svgp_small_predict.restype = c_int
+        lib.gpx_svgp_small_predict.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_int, c_int, c_void_p, c_void_p, c_int_p, c_void_p]
+        lib.gpx_svgp_small_destroy.restype = c_int
+        lib.gpx_svgp_small_destroy.argtypes = [c_void_p]
         lib.gpx_sgpr_create.restype = c_int
         lib.gpx_sgpr_create.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, spec_p,
                                         ctypes.POINTER(c_void_p)]

@@ -765,6 +765,140 @@ class SVGPEngine:
         return mean, var
 
 
+def svgp_small_limits():
+    """(M, N) limits of the fused small-shape SVGP path (gpx_svgp_small_limits; needs no device)."""
+    lib = N.load_library()
+    m, n = ctypes.c_int(0), ctypes.c_int(0)
+    rc = lib.gpx_svgp_small_limits(ctypes.byref(m), ctypes.byref(n))
+    if rc != N.GPX_OK:
+        raise N.GPXError(f"gpx_svgp_small_limits failed ({rc})")
+    return int(m.value), int(n.value)
+
+
+class SVGPSmallEngine:
+    """A batch of small SVGP models evaluated in one fused launch (include/gpx.h gpx_svgp_small):
+    ``B`` slots for models of one input dimension ``D`` with at most ``N_max`` rows and ``M_max``
+    inducing points, one workgroup per model. The per-call arrays are host numpy arrays indexed by
+    slot, in the C layout: ``theta [B, 16]``, ``Z [B, M_max·D]``, ``q_mu [B, M_max]``,
+    ``q_sqrt [B, M_max·M_max]``, each row holding the slot's own compact [m, D] / [m] / [m, m]
+    values at its start (``pack``)."""
+
+    def __init__(self, B: int, N_max: int, M_max: int, D: int, device: Optional[int] = None):
+        self.device = require_gpu(device)
+        self.ctx = N.Context.get(self.device)
+        self.lib = self.ctx.lib
+        self.B, self.N_max, self.M_max, self.D = int(B), int(N_max), int(M_max), int(D)
+        h = ctypes.c_void_p()
+        rc = self.lib.gpx_svgp_small_create(self.ctx.handle, self.B, self.N_max, self.M_max, self.D,
+                                            ctypes.byref(h))
+        if rc != N.GPX_OK:
+            raise N.GPXError(f"gpx_svgp_small_create failed ({rc}): {self.ctx.last_error()}")
+        self.handle = h
+        self.n = [0] * self.B
+        self.m = [0] * self.B
+        self.specs = [None] * self.B
+        sz, sr = self.M_max * self.D, self.M_max * self.M_max
+        # per-call inputs and outputs, one row per slot (rows of inactive slots keep stale values)
+        self.theta = np.ones((self.B, N.GPX_THETA_STRIDE))
+        self.Z = np.zeros((self.B, sz))
+        self.q_mu = np.zeros((self.B, self.M_max))
+        self.q_sqrt = np.zeros((self.B, sr))
+        self.elbo = np.zeros(self.B)
+        self.g_theta = np.zeros((self.B, N.GPX_THETA_STRIDE))
+        self.g_Z = np.zeros((self.B, sz))
+        self.g_q_mu = np.zeros((self.B, self.M_max))
+        self.g_q_sqrt = np.zeros((self.B, sr))
+        self.info = np.zeros(self.B, dtype=np.int32)
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h is not None and h.value:
+            try:
+                self.lib.gpx_svgp_small_destroy(h)
+            except Exception:
+                pass
+            self.handle = None
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def bind(self, b: int, X, Y, spec: N.GpxKernelSpec, M: int, num_data: Optional[float] = None) -> None:
+        """Copy a model's data into slot ``b`` (X [n, D], Y [n]; ``M`` inducing points)."""
+        x = _host_f64(X)
+        x = np.ascontiguousarray(x.reshape(x.shape[0], -1))
+        y = np.ascontiguousarray(_host_f64(Y).reshape(-1))
+        if x.shape[1] != self.D:
+            raise ValueError(f"X must have {self.D} columns")
+        if y.shape[0] != x.shape[0]:
+            raise ValueError("X and Y must have the same number of rows")
+        n = int(x.shape[0])
+        rc = self.lib.gpx_svgp_small_bind(self.handle, int(b), n, int(M), ctypes.c_void_p(x.ctypes.data),
+                                          ctypes.c_void_p(y.ctypes.data), ctypes.byref(spec),
+                                          float(n if num_data is None else num_data))
+        if rc != N.GPX_OK:
+            raise N.GPXError(f"gpx_svgp_small_bind failed ({rc}): {self.ctx.last_error()}")
+        self.n[b], self.m[b], self.specs[b] = n, int(M), spec
+
+    def pack(self, b: int, theta, Z, q_mu, q_sqrt) -> None:
+        """Slot ``b``'s state into its rows of the call arrays."""
+        m, D = self.m[b], self.D
+        self.theta[b] = np.asarray(theta, dtype=np.float64).reshape(N.GPX_THETA_STRIDE)
+        self.Z[b, :m * D] = np.asarray(Z, dtype=np.float64).reshape(m * D)
+        self.q_mu[b, :m] = np.asarray(q_mu, dtype=np.float64).reshape(m)
+        self.q_sqrt[b, :m * m] = np.asarray(q_sqrt, dtype=np.float64).reshape(m * m)
+
+    def elbo_grad(self, active: Sequence[int]):
+        """Evaluate the listed slots from the call arrays. Returns ``info`` (a copy: 0, or the failing
+        pivot of a slot whose Kuu + jitter I is not positive definite — the other slots' results are
+        valid either way); ``result(b)`` reads a slot's outputs."""
+        act = np.ascontiguousarray(np.asarray(active, dtype=np.int32).reshape(-1))
+        vp = lambda a: ctypes.c_void_p(a.ctypes.data)  # noqa: E731
+        rc = self.lib.gpx_svgp_small_elbo_grad(
+            self.handle, int(act.shape[0]), act.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+            vp(self.theta), vp(self.Z), vp(self.q_mu), vp(self.q_sqrt), vp(self.elbo), vp(self.g_theta),
+            vp(self.g_Z), vp(self.g_q_mu), vp(self.g_q_sqrt),
+            self.info.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), self._stream())
+        if rc not in (N.GPX_OK, N.GPX_NOT_PD):
+            raise N.GPXError(f"gpx_svgp_small_elbo_grad failed ({rc}): {self.ctx.last_error()}")
+        return self.info.copy()
+
+    def result(self, b: int):
+        """(elbo, ∂θ [16], ∂Z [m, D], ∂q_mu [m], ∂q_sqrt [m, m]) of slot ``b``'s last evaluation."""
+        m, D = self.m[b], self.D
+        return (float(self.elbo[b]), self.g_theta[b].copy(), self.g_Z[b, :m * D].reshape(m, D).copy(),
+                self.g_q_mu[b, :m].copy(), self.g_q_sqrt[b, :m * m].reshape(m, m).copy())
+
+    @staticmethod
+    def not_pd(pivot: int) -> N.NotPositiveDefiniteError:
+        return N.NotPositiveDefiniteError(
+            f"Cholesky decomposition was not successful (pivot {int(pivot)}): "
+            "Kuu + jitter I is not positive definite", int(pivot))
+
+    def predict(self, b: int, theta, Z, q_mu, q_sqrt, Xnew, add_noise: bool):
+        """predict_f / predict_y of slot ``b`` at Xnew -> (mean [Mn], var [Mn]) host arrays."""
+        m, D = self.m[b], self.D
+        x = _host_f64(Xnew)
+        x = np.ascontiguousarray(x.reshape(0, D) if x.size == 0 else x.reshape(x.shape[0], -1))
+        if x.shape[1] != D:
+            raise ValueError(f"Xnew must have {D} columns")
+        Mn = int(x.shape[0])
+        mean, var = np.empty(Mn), np.empty(Mn)
+        if Mn == 0:
+            return mean, var
+        host = SVGPEngine._host
+        keep = (host(theta, (N.GPX_THETA_STRIDE,)), host(Z, (m, D)), host(q_mu, (m,)), host(q_sqrt, (m, m)))
+        info = ctypes.c_int32(0)
+        vp = lambda a: ctypes.c_void_p(a.ctypes.data)  # noqa: E731
+        rc = self.lib.gpx_svgp_small_predict(self.handle, int(b), *[vp(a) for a in keep], vp(x), Mn,
+                                             1 if add_noise else 0, vp(mean), vp(var), ctypes.byref(info),
+                                             self._stream())
+        if rc == N.GPX_NOT_PD:
+            raise self.not_pd(info.value)
+        if rc != N.GPX_OK:
+            raise N.GPXError(f"gpx_svgp_small_predict failed ({rc}): {self.ctx.last_error()}")
+        return mean, var
+
+
 class SGPREngine:
     """Device state of one SGPR model (include/gpx.h gpx_sgpr): X [N, D] / Y [N] resident in
     HBM, Kmn and the two M x M factorisations' workspace owned by the library."""

@@ -486,6 +486,27 @@ class SVGP:
         return m, v
 
 
+def predict_f_svgp_batch(models: Sequence[SVGP], Xnews: Sequence, add_noise: bool = False):
+    """predict_f (or predict_y) of several SVGP models fitted by Scipy().minimize_svgp_batch, over the
+    engine they are bound to (gpx_svgp_small_predict, one slot per model). A model that is not bound
+    to one (over the fused path's limits, or never fitted in a batch) is predicted by its own
+    predict_f / predict_y. Returns [(mean [Mn, 1], var [Mn, 1])] like the models' own methods."""
+    out = []
+    for m, x in zip(models, Xnews):
+        bound = getattr(m, "_small", None)
+        if bound is None:
+            out.append(m.predict_y(x) if add_noise else m.predict_f(x))
+            continue
+        eng, b = bound
+        mean, var = eng.predict(b, *m._state(), x, add_noise)
+        mean = torch.from_numpy(mean).reshape(-1, 1)
+        var = torch.from_numpy(var).reshape(-1, 1)
+        if isinstance(x, torch.Tensor) and x.is_cuda:
+            mean, var = mean.to(x.device), var.to(x.device)
+        out.append((mean, var))
+    return out
+
+
 class SGPR:
     """gpflow.models.SGPR: sparse GP regression by the collapsed (Titsias) bound, Gaussian
     likelihood, zero mean, one output — the cell at test_scripts/SVGP.py:395-412::

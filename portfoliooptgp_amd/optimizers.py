@@ -333,6 +333,129 @@ class Scipy:
                 raise e
         return results  # type: ignore[return-value]
 
+    def minimize_svgp_batch(self, models: Sequence, data, method: str = "L-BFGS-B", on_not_pd: str = "raise",
+                            **scipy_kwargs) -> List[scipy.optimize.OptimizeResult]:
+        """Fit several models.SVGP (Gaussian likelihood, closed-form route) in lock-step: the sweep of
+        the reference's train_svgp_model (test_scripts/GPR.py:118-138). ``data`` is one ``(X, Y)``
+        for every model or one pair per model; the models must share the input dimension.
+
+        Each model runs its own unmodified L-BFGS-B, stepped as ``minimize``'s solo branch steps it
+        (lbfgsb.BatchStepper, one slot, or LbfgsbStepper), so variable counts may differ. Each
+        round, every model waiting for a value is evaluated in ONE gpx_svgp_small_elbo_grad call
+        (engine.SVGPSmallEngine: one workgroup per model); finished models drop out. The chain rule
+        is SVGP.grads_to_unconstrained's. A model's evaluation does not depend on what shares its
+        call, so its trajectory is the one it has when fitted alone by this method.
+
+        A model over the fused path's limits (M > 32 or N > 4096) stays in the loop and is evaluated
+        by its own SVGPEngine: its trajectory is ``minimize``'s. ``on_not_pd`` as in minimize_batch.
+        Results are written back into the models, which stay bound to the shared engine for
+        models.predict_f_svgp_batch."""
+        from .engine import SVGPSmallEngine, svgp_small_limits
+        from .likelihoods import StudentT
+        from .models import SVGP
+        as_inf = _not_pd_policy(on_not_pd)
+        models = list(models)
+        if not models:
+            return []
+        if not lbfgsb.supports(method, scipy_kwargs):
+            raise NotImplementedError("minimize_svgp_batch runs plain unbounded L-BFGS-B (method='L-BFGS-B', "
+                                      "options= of maxcor/ftol/gtol/maxfun/maxiter/maxls): fit with Scipy().minimize "
+                                      "for anything else")
+        if (isinstance(data, tuple) and len(data) == 2
+                and not isinstance(data[0], (tuple, list))):
+            datas = [data] * len(models)
+        else:
+            datas = [tuple(d) for d in data]
+            if len(datas) != len(models) or any(len(d) != 2 for d in datas):
+                raise ValueError("data must be one (X, Y) pair, or one pair per model")
+        for i, m in enumerate(models):
+            if not isinstance(m, SVGP):
+                raise TypeError(f"model {i} is not a models.SVGP")
+            if isinstance(m.likelihood, StudentT):
+                raise NotImplementedError(f"minimize_svgp_batch: model {i} has the StudentT likelihood, which is "
+                                          "evaluated by the per-point route; fit it with Scipy().minimize")
+            if m.per_point:
+                raise NotImplementedError(f"minimize_svgp_batch: model {i} was built with per_point=True; the "
+                                          "batched path is the closed-form Gaussian route. Fit it with "
+                                          "Scipy().minimize")
+        shapes = []
+        for X, _ in datas:
+            sh = tuple(X.shape) if hasattr(X, "shape") else np.shape(X)
+            shapes.append((int(sh[0]), 1 if len(sh) == 1 else int(sh[1])))
+        dims = sorted({d for _, d in shapes})
+        if len(dims) != 1:
+            raise ValueError(f"minimize_svgp_batch: the models must share the input dimension D, got {dims}")
+        D = dims[0]
+        m_lim, n_lim = svgp_small_limits()
+        small = [i for i, m in enumerate(models) if m.M <= m_lim and shapes[i][0] <= n_lim]
+        slot = {i: s for s, i in enumerate(small)}
+        eng = None
+        if small:
+            eng = SVGPSmallEngine(len(small), max(shapes[i][0] for i in small), max(models[i].M for i in small), D,
+                                  device=models[small[0]].device)
+            for i in small:
+                m = models[i]
+                eng.bind(slot[i], datas[i][0], datas[i][1], compile_spec(m.kernel, D), m.M,
+                         num_data=None if m.num_data is None else float(m.num_data))
+                m._small = (eng, slot[i])
+        opts = scipy_kwargs.get("options") or {}
+        variables, steppers, solo = [], [], {}
+        for i, m in enumerate(models):
+            v = tuple(m.trainable_variables)
+            if not v:
+                raise ValueError("model has no trainable variables")
+            x0 = _pack(v)
+            variables.append(v)
+            steppers.append(lbfgsb.BatchStepper(1, len(x0), opts).start(0, x0) if lbfgsb.BatchStepper.NATIVE
+                            else lbfgsb.LbfgsbStepper(x0, opts))
+            if i not in slot:  # over the limits: minimize's own evaluation, through the model's engine
+                lg = m.training_loss_closure(datas[i])._gpx_loss_and_grad
+
+                def func(x, v=v, lg=lg):
+                    _unpack(v, x)
+                    return lg(v)
+                solo[i] = _guarded(func, as_inf)
+
+        def failed(i, err):
+            if not as_inf:
+                raise err
+            return float("inf"), np.zeros(len(steppers[i].x))
+
+        active = list(range(len(models)))
+        with _single_thread_blas():
+            while active:
+                out, call = {}, []
+                for i in active:
+                    if i in solo:
+                        out[i] = solo[i](steppers[i].x)
+                        continue
+                    m = models[i]
+                    _unpack(variables[i], steppers[i].x)
+                    theta, Z, q, R = m._state()
+                    npar = len(m.kernel.parameters) + 1
+                    if not (np.all(np.isfinite(theta[:npar])) and np.all(theta[:npar] > 0.0)
+                            and np.all(np.isfinite(Z)) and np.all(np.isfinite(q)) and np.all(np.isfinite(R))):
+                        out[i] = failed(i, N.InvalidParameterError(
+                            f"model {i}: a hyperparameter left (0, inf) or a variational parameter is not finite"))
+                        continue
+                    eng.pack(slot[i], theta, Z, q, R)
+                    call.append(i)
+                if call:
+                    info = eng.elbo_grad([slot[i] for i in call])
+                    for i in call:
+                        if info[slot[i]] != 0:
+                            out[i] = failed(i, eng.not_pd(info[slot[i]]))
+                        else:
+                            out[i] = models[i].grads_to_unconstrained(variables[i], *eng.result(slot[i]))
+                for i in active:
+                    steppers[i].tell(*out[i])
+                active = [i for i in active if not steppers[i].done]
+        results = []
+        for v, st in zip(variables, steppers):
+            res = st.result()
+            _unpack(v, res.x)
+            results.append(res)
+        return results
 
     def minimize_stream(self, models: Sequence, width: int, method: str = "L-BFGS-B",
                         device: Optional[int] = None, predict_train: bool = False,

@@ -6,6 +6,8 @@
   lock-step batch; each is the same scipy trajectory it would be alone. Kernel objects are
   shared across calls exactly as in the reference (later fits warm-start from the
   previous optimum and earlier best models alias the mutated kernels).
+* ``ModelTrainer.train_svgp_model`` — test_scripts/GPR.py:118-138: the same sweep with one SVGP per
+  kernel (Gaussian(1e-4) frozen, inducing points X[:20]), fitted by ``Scipy().minimize_svgp_batch``.
 * ``Predictor`` — GPR/predictor.py:4-51 (predict_single; predict_combined and
   upsample_predictions as host post-processing).
 * ``MultiInputTrainer`` — Multi-Input_GPR/models/model_trainer.py:17-72 (train_model,
@@ -55,6 +57,30 @@ class ModelTrainer:
         self.last_results = Scipy().minimize_batch(models, options=dict(maxiter=maxiter))
         self.last_models = models
         preds = M.predict_f_batch(models, [m.data[0] for m in models])
+        best_kernel, best_mse, best_model = None, float("inf"), None
+        for kernel, model, (mean, _) in zip(self.kernel_combinations, models, preds):
+            mse = mean_squared_error(Y_tf, _np(mean))
+            if mse < best_mse:
+                best_mse, best_kernel, best_model = mse, kernel, model
+        return best_kernel, best_mse, best_model
+
+    def train_svgp_model(self, X_tf, Y_tf, n_inducing: int = 20, maxiter: int = 100):
+        """test_scripts/GPR.py:118-138: per kernel an SVGP with Gaussian(1e-4) frozen and the first
+        ``n_inducing`` training inputs as inducing points (num_data left None), L-BFGS-B
+        maxiter=100, predict_f at the training X, the minimum training MSE wins (strict ``<``,
+        first wins). The kernel fits run in one lock-step batch, one device call per round."""
+        from .likelihoods import Gaussian
+        Z0 = _np(X_tf)
+        Z0 = Z0.reshape(Z0.shape[0], -1)[:n_inducing]
+        models = []
+        for kernel in self.kernel_combinations:
+            model = M.SVGP(kernel=kernel, likelihood=Gaussian(variance=1e-4), inducing_variable=Z0.copy(),
+                           device=self.device)
+            set_trainable(model.likelihood.variance, False)
+            models.append(model)
+        self.last_results = Scipy().minimize_svgp_batch(models, (X_tf, Y_tf), options=dict(maxiter=maxiter))
+        self.last_models = models
+        preds = M.predict_f_svgp_batch(models, [X_tf] * len(models))
         best_kernel, best_mse, best_model = None, float("inf"), None
         for kernel, model, (mean, _) in zip(self.kernel_combinations, models, preds):
             mse = mean_squared_error(Y_tf, _np(mean))
