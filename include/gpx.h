@@ -529,6 +529,46 @@ int gpx_sgpr_predict(gpx_sgpr* sgpr, const double* theta, const double* Z, const
                      int add_noise, double* mean, double* var, int32_t* info, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * A batch of small SGPR models, one fused launch per call: a sweep of the reference's SGPR cell
+ * (test_scripts/SVGP.py:393-400: SGPR((X, Y), SquaredExponential(), inducing_variable =
+ * np.linspace(0, 360, 10)[:, None]), N ≈ 113, M = 10) over kernels, inducing counts and series. The
+ * model and its arithmetic are gpx_sgpr_create's (collapsed bound, Gaussian likelihood, zero mean,
+ * jitter 1e-6, explicit W = L⁻¹ and WB = LB⁻¹); each model is evaluated whole by one workgroup, in
+ * two passes over its data. Limits (gpx_sgpr_small_limits; over them GPX_BAD_ARG): M <= 32,
+ * N <= 4096, D <= GPX_MAX_DIM; specs with GPX_TERM_ARD are refused as by gpx_sgpr_create.
+ *
+ * An object has B slots for models of one input dimension D with n <= N_max rows and m <= M_max
+ * inducing points. gpx_sgpr_small_bind copies a model's X [n, D] and Y [n] (host, fp64) into slot b.
+ * Per call, all host fp64 arrays indexed by SLOT, of which only the rows of the active slots are
+ * read / written, and of a row only the model's own leading entries (its tail is never read):
+ *   theta   [B][16]           kernel params then σn² at theta[n_params], as gpx_sgpr_elbo_grad
+ *   Z       [B][M_max·D]      the slot's [m, D] inducing inputs, row-major, at the row's start
+ * Outputs: elbo [B]; grad_theta [B][16]; grad_Z in the layout of Z; info [B][2]: the 1-based index of
+ * the first pivot that is not > 0 of Kmm + 1e-6 I (info[b][0]) and of B = I + L⁻¹ Kmn Kmnᵀ L⁻ᵀ/σn²
+ * (info[b][1]), else 0. GPX_NOT_PD when some active slot's info != 0 — that slot's outputs are then
+ * unspecified, the other slots' stay valid. theta not finite or <= 0 and a non-finite Z return
+ * GPX_BAD_ARG before anything is launched.
+ * A model's outputs are a function of its own inputs alone, bit for bit: they do not depend on B,
+ * on its slot, on its place in `active`, or on what else the call evaluates.
+ * gpx_sgpr_small_predict: predict_f (add_noise = 0) / predict_y (1) of slot b at Xnew (HOST
+ * [Mn, D]) -> mean, var (HOST [Mn]); theta [16] and Z [m, D] of that one model; info points to two
+ * int32. Mn = 0 is allowed and writes nothing.
+ * Calls return when the outputs are filled; one object serves one thread at a time.
+ */
+typedef struct gpx_sgpr_small gpx_sgpr_small;
+int gpx_sgpr_small_limits(int* m_max, int* n_max); /* 32, 4096; needs no device */
+int gpx_sgpr_small_create(gpx_ctx* ctx, int B, int N_max, int M_max, int D, gpx_sgpr_small** out);
+int gpx_sgpr_small_bind(gpx_sgpr_small* small, int b, int n, int m, const double* X, const double* Y,
+                        const gpx_kernel_spec* spec);
+int gpx_sgpr_small_elbo_grad(gpx_sgpr_small* small, int n_active, const int32_t* active,
+                             const double* theta, const double* Z, double* elbo, double* grad_theta,
+                             double* grad_Z, int32_t* info, void* stream);
+int gpx_sgpr_small_predict(gpx_sgpr_small* small, int b, const double* theta, const double* Z,
+                           const double* Xnew, int Mn, int add_noise, double* mean, double* var,
+                           int32_t* info, void* stream);
+int gpx_sgpr_small_destroy(gpx_sgpr_small* small);
+
+/* ---------------------------------------------------------------------------------------
  * VGP: gpflow.models.VGP((X, Y), kernel, likelihood) with GPflow's defaults — whitened
  * q(f) = N(L q_mu, L q_sqrt q_sqrtᵀ Lᵀ), L = chol(k(X,X) + 1e-6 I), full q_sqrt, zero mean, one
  * output; test_scripts/SVGP.py:402-437 (SE kernel, StudentT likelihood, N ≈ 113).

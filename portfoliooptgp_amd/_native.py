@@ -50,6 +50,8 @@ EXPORTED_SYMBOLS = (
     "gpx_svgp_small_limits", "gpx_svgp_small_create", "gpx_svgp_small_bind", "gpx_svgp_small_elbo_grad",
     "gpx_svgp_small_predict", "gpx_svgp_small_destroy",
     "gpx_sgpr_create", "gpx_sgpr_destroy", "gpx_sgpr_elbo_grad", "gpx_sgpr_predict",
+    "gpx_sgpr_small_limits", "gpx_sgpr_small_create", "gpx_sgpr_small_bind", "gpx_sgpr_small_elbo_grad",
+    "gpx_sgpr_small_predict", "gpx_sgpr_small_destroy",
     "gpx_vgp_create", "gpx_vgp_destroy", "gpx_vgp_elbo_grad", "gpx_vgp_predict",
     "gpx_host_theta_rows", "gpx_host_loss_grad_u",
     "gpx_batch_set_mean", "gpx_host_theta_rows_t", "gpx_host_loss_grad_u_t",
@@ -259,6 +261,19 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.gpx_sgpr_predict.restype = c_int
         lib.gpx_sgpr_predict.argtypes = [c_void_p, c_double_p, c_double_p, c_void_p, c_int, c_int,
                                          c_void_p, c_void_p, c_int_p, c_void_p]
+        lib.gpx_sgpr_small_limits.restype = c_int
+        lib.gpx_sgpr_small_limits.argtypes = [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
+        lib.gpx_sgpr_small_create.restype = c_int
+        lib.gpx_sgpr_small_create.argtypes = [c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p)]
+        lib.gpx_sgpr_small_bind.restype = c_int
+        lib.gpx_sgpr_small_bind.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, spec_p]
+        lib.gpx_sgpr_small_elbo_grad.restype = c_int
+        lib.gpx_sgpr_small_elbo_grad.argtypes = [c_void_p, c_int, c_int_p] + [c_void_p] * 5 + [c_int_p, c_void_p]
+        lib.gpx_sgpr_small_predict.restype = c_int
+        lib.gpx_sgpr_small_predict.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                               c_void_p, c_void_p, c_int_p, c_void_p]
+        lib.gpx_sgpr_small_destroy.restype = c_int
+        lib.gpx_sgpr_small_destroy.argtypes = [c_void_p]
         lib.gpx_vgp_create.restype = c_int
         lib.gpx_vgp_create.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, spec_p, c_int, c_double,
                                        ctypes.POINTER(c_void_p)]

@@ -982,6 +982,132 @@ class SGPREngine:
         return mean, var
 
 
+def sgpr_small_limits():
+    """(M, N) limits of the fused small-shape SGPR path (gpx_sgpr_small_limits; needs no device)."""
+    lib = N.load_library()
+    m, n = ctypes.c_int(0), ctypes.c_int(0)
+    rc = lib.gpx_sgpr_small_limits(ctypes.byref(m), ctypes.byref(n))
+    if rc != N.GPX_OK:
+        raise N.GPXError(f"gpx_sgpr_small_limits failed ({rc})")
+    return int(m.value), int(n.value)
+
+
+class SGPRSmallEngine:
+    """A batch of small SGPR models evaluated in one fused launch (include/gpx.h gpx_sgpr_small):
+    ``B`` slots for models of one input dimension ``D`` with at most ``N_max`` rows and ``M_max``
+    inducing points, one workgroup per model. The per-call arrays are host numpy arrays indexed by
+    slot, in the C layout: ``theta [B, 16]``, ``Z [B, M_max·D]``, each row holding the slot's own
+    compact [m, D] values at its start (``pack``)."""
+
+    def __init__(self, B: int, N_max: int, M_max: int, D: int, device: Optional[int] = None):
+        self.device = require_gpu(device)
+        self.ctx = N.Context.get(self.device)
+        self.lib = self.ctx.lib
+        self.B, self.N_max, self.M_max, self.D = int(B), int(N_max), int(M_max), int(D)
+        h = ctypes.c_void_p()
+        rc = self.lib.gpx_sgpr_small_create(self.ctx.handle, self.B, self.N_max, self.M_max, self.D,
+                                            ctypes.byref(h))
+        if rc != N.GPX_OK:
+            raise N.GPXError(f"gpx_sgpr_small_create failed ({rc}): {self.ctx.last_error()}")
+        self.handle = h
+        self.n = [0] * self.B
+        self.m = [0] * self.B
+        self.specs = [None] * self.B
+        sz = self.M_max * self.D
+        # per-call inputs and outputs, one row per slot (rows of inactive slots keep stale values)
+        self.theta = np.ones((self.B, N.GPX_THETA_STRIDE))
+        self.Z = np.zeros((self.B, sz))
+        self.elbo = np.zeros(self.B)
+        self.g_theta = np.zeros((self.B, N.GPX_THETA_STRIDE))
+        self.g_Z = np.zeros((self.B, sz))
+        self.info = np.zeros((self.B, 2), dtype=np.int32)
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h is not None and h.value:
+            try:
+                self.lib.gpx_sgpr_small_destroy(h)
+            except Exception:
+                pass
+            self.handle = None
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def bind(self, b: int, X, Y, spec: N.GpxKernelSpec, M: int) -> None:
+        """Copy a model's data into slot ``b`` (X [n, D], Y [n]; ``M`` inducing points)."""
+        x = _host_f64(X)
+        x = np.ascontiguousarray(x.reshape(x.shape[0], -1))
+        y = np.ascontiguousarray(_host_f64(Y).reshape(-1))
+        if x.shape[1] != self.D:
+            raise ValueError(f"X must have {self.D} columns")
+        if y.shape[0] != x.shape[0]:
+            raise ValueError("X and Y must have the same number of rows")
+        n = int(x.shape[0])
+        rc = self.lib.gpx_sgpr_small_bind(self.handle, int(b), n, int(M), ctypes.c_void_p(x.ctypes.data),
+                                          ctypes.c_void_p(y.ctypes.data), ctypes.byref(spec))
+        if rc != N.GPX_OK:
+            raise N.GPXError(f"gpx_sgpr_small_bind failed ({rc}): {self.ctx.last_error()}")
+        self.n[b], self.m[b], self.specs[b] = n, int(M), spec
+
+    def pack(self, b: int, theta, Z) -> None:
+        """Slot ``b``'s state into its rows of the call arrays."""
+        m, D = self.m[b], self.D
+        self.theta[b] = np.asarray(theta, dtype=np.float64).reshape(N.GPX_THETA_STRIDE)
+        self.Z[b, :m * D] = np.asarray(Z, dtype=np.float64).reshape(m * D)
+
+    def elbo_grad(self, active: Sequence[int]):
+        """Evaluate the listed slots from the call arrays. Returns ``info`` (a copy, [B, 2]: per slot
+        0, or the failing pivot of Kuu + jitter I / of B = I + A Aᵀ — the other slots' results are
+        valid either way); ``result(b)`` reads a slot's outputs."""
+        act = np.ascontiguousarray(np.asarray(active, dtype=np.int32).reshape(-1))
+        vp = lambda a: ctypes.c_void_p(a.ctypes.data)  # noqa: E731
+        rc = self.lib.gpx_sgpr_small_elbo_grad(
+            self.handle, int(act.shape[0]), act.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+            vp(self.theta), vp(self.Z), vp(self.elbo), vp(self.g_theta), vp(self.g_Z),
+            self.info.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), self._stream())
+        if rc not in (N.GPX_OK, N.GPX_NOT_PD):
+            raise N.GPXError(f"gpx_sgpr_small_elbo_grad failed ({rc}): {self.ctx.last_error()}")
+        return self.info.copy()
+
+    def result(self, b: int):
+        """(elbo, ∂θ [16], ∂Z [m, D]) of slot ``b``'s last evaluation."""
+        m, D = self.m[b], self.D
+        return float(self.elbo[b]), self.g_theta[b].copy(), self.g_Z[b, :m * D].reshape(m, D).copy()
+
+    @staticmethod
+    def not_pd(info_pair) -> N.NotPositiveDefiniteError:
+        """The error of a slot whose ``info`` pair is not (0, 0), worded as SGPREngine words it."""
+        which, pivot = (("Kuu + jitter I", int(info_pair[0])) if info_pair[0] != 0
+                        else ("B = I + A Aᵀ", int(info_pair[1])))
+        return N.NotPositiveDefiniteError(
+            f"Cholesky decomposition was not successful (pivot {pivot}): {which} is not positive definite",
+            pivot)
+
+    def predict(self, b: int, theta, Z, Xnew, add_noise: bool):
+        """predict_f / predict_y of slot ``b`` at Xnew -> (mean [Mn], var [Mn]) host arrays."""
+        m, D = self.m[b], self.D
+        x = _host_f64(Xnew)
+        x = np.ascontiguousarray(x.reshape(0, D) if x.size == 0 else x.reshape(x.shape[0], -1))
+        if x.shape[1] != D:
+            raise ValueError(f"Xnew must have {D} columns")
+        Mn = int(x.shape[0])
+        mean, var = np.empty(Mn), np.empty(Mn)
+        if Mn == 0:
+            return mean, var
+        host = SVGPEngine._host
+        keep = (host(theta, (N.GPX_THETA_STRIDE,)), host(Z, (m, D)))
+        info = (ctypes.c_int32 * 2)(0, 0)
+        vp = lambda a: ctypes.c_void_p(a.ctypes.data)  # noqa: E731
+        rc = self.lib.gpx_sgpr_small_predict(self.handle, int(b), vp(keep[0]), vp(keep[1]), vp(x), Mn,
+                                             1 if add_noise else 0, vp(mean), vp(var), info, self._stream())
+        if rc == N.GPX_NOT_PD:
+            raise self.not_pd(info)
+        if rc != N.GPX_OK:
+            raise N.GPXError(f"gpx_sgpr_small_predict failed ({rc}): {self.ctx.last_error()}")
+        return mean, var
+
+
 class VGPEngine:
     """Device state of one VGP model (include/gpx.h gpx_vgp): X [N, D] / Y [N] resident in HBM,
     the N x N factorisation and GEMM workspace owned by the library. ``likelihood`` is

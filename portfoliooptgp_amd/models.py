@@ -665,6 +665,27 @@ class SGPR:
         return m, v
 
 
+def predict_f_sgpr_batch(models: Sequence[SGPR], Xnews: Sequence, add_noise: bool = False):
+    """predict_f (or predict_y) of several SGPR models fitted by Scipy().minimize_sgpr_batch, over the
+    engine they are bound to (gpx_sgpr_small_predict, one slot per model). A model that is not bound
+    to one (over the fused path's limits, or never fitted in a batch) is predicted by its own
+    predict_f / predict_y. Returns [(mean [Mn, 1], var [Mn, 1])] like the models' own methods."""
+    out = []
+    for m, x in zip(models, Xnews):
+        bound = getattr(m, "_small", None)
+        if bound is None:
+            out.append(m.predict_y(x) if add_noise else m.predict_f(x))
+            continue
+        eng, b = bound
+        mean, var = eng.predict(b, *m._state(), x, add_noise)
+        mean = torch.from_numpy(mean).reshape(-1, 1)
+        var = torch.from_numpy(var).reshape(-1, 1)
+        if isinstance(x, torch.Tensor) and x.is_cuda:
+            mean, var = mean.to(x.device), var.to(x.device)
+        out.append((mean, var))
+    return out
+
+
 class VGP:
     """gpflow.models.VGP with GPflow's defaults (whitened, full q_sqrt, zero mean, one latent GP)
     and a Gaussian or StudentT likelihood — the cell at test_scripts/SVGP.py:402-437::

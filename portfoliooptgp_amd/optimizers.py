@@ -457,6 +457,111 @@ class Scipy:
             results.append(res)
         return results
 
+    def minimize_sgpr_batch(self, models: Sequence, method: str = "L-BFGS-B", on_not_pd: str = "raise",
+                            **scipy_kwargs) -> List[scipy.optimize.OptimizeResult]:
+        """Fit several models.SGPR in lock-step: a sweep of the reference's SGPR cell
+        (test_scripts/SVGP.py:393-400) over kernels, inducing counts and series. Each model keeps its
+        own data (``model.data``); the models must share the input dimension.
+
+        Each model runs its own unmodified L-BFGS-B, stepped as ``minimize``'s solo branch steps it
+        (lbfgsb.BatchStepper, one slot, or LbfgsbStepper), so variable counts may differ. Each
+        round, every model waiting for a value is evaluated in ONE gpx_sgpr_small_elbo_grad call
+        (engine.SGPRSmallEngine: one workgroup per model); finished models drop out. The chain rule
+        is SGPR.grads_to_unconstrained's. A model's evaluation does not depend on what shares its
+        call, so its trajectory is the one it has when fitted alone by this method.
+
+        A model over the fused path's limits (M > 32 or N > 4096) stays in the loop and is evaluated
+        by its own SGPREngine: its trajectory is ``minimize``'s. ``on_not_pd`` as in minimize_batch.
+        Results are written back into the models, which stay bound to the shared engine for
+        models.predict_f_sgpr_batch."""
+        from .engine import SGPRSmallEngine, sgpr_small_limits
+        from .models import SGPR
+        as_inf = _not_pd_policy(on_not_pd)
+        models = list(models)
+        if not models:
+            return []
+        if not lbfgsb.supports(method, scipy_kwargs):
+            raise NotImplementedError("minimize_sgpr_batch runs plain unbounded L-BFGS-B (method='L-BFGS-B', "
+                                      "options= of maxcor/ftol/gtol/maxfun/maxiter/maxls): fit with Scipy().minimize "
+                                      "for anything else")
+        for i, m in enumerate(models):
+            if not isinstance(m, SGPR):
+                raise TypeError(f"model {i} is not a models.SGPR")
+        shapes = [(int(m.data[0].shape[0]), int(m.data[0].shape[1])) for m in models]
+        dims = sorted({d for _, d in shapes})
+        if len(dims) != 1:
+            raise ValueError(f"minimize_sgpr_batch: the models must share the input dimension D, got {dims}")
+        D = dims[0]
+        m_lim, n_lim = sgpr_small_limits()
+        small = [i for i, m in enumerate(models) if m.M <= m_lim and shapes[i][0] <= n_lim]
+        slot = {i: s for s, i in enumerate(small)}
+        eng = None
+        if small:
+            eng = SGPRSmallEngine(len(small), max(shapes[i][0] for i in small), max(models[i].M for i in small), D,
+                                  device=models[small[0]].device)
+            for i in small:
+                m = models[i]
+                eng.bind(slot[i], m.data[0], m.data[1], compile_spec(m.kernel, D), m.M)
+                m._small = (eng, slot[i])
+        opts = scipy_kwargs.get("options") or {}
+        variables, steppers, solo = [], [], {}
+        for i, m in enumerate(models):
+            v = tuple(m.trainable_variables)
+            if not v:
+                raise ValueError("model has no trainable variables")
+            x0 = _pack(v)
+            variables.append(v)
+            steppers.append(lbfgsb.BatchStepper(1, len(x0), opts).start(0, x0) if lbfgsb.BatchStepper.NATIVE
+                            else lbfgsb.LbfgsbStepper(x0, opts))
+            if i not in slot:  # over the limits: minimize's own evaluation, through the model's engine
+                m._small = None
+
+                def func(x, v=v, lg=m.loss_and_grad_unconstrained):
+                    _unpack(v, x)
+                    return lg(v)
+                solo[i] = _guarded(func, as_inf)
+
+        def failed(i, err):
+            if not as_inf:
+                raise err
+            return float("inf"), np.zeros(len(steppers[i].x))
+
+        active = list(range(len(models)))
+        with _single_thread_blas():
+            while active:
+                out, call = {}, []
+                for i in active:
+                    if i in solo:
+                        out[i] = solo[i](steppers[i].x)
+                        continue
+                    m = models[i]
+                    _unpack(variables[i], steppers[i].x)
+                    theta, Z = m._state()
+                    npar = len(m.kernel.parameters) + 1
+                    if not (np.all(np.isfinite(theta[:npar])) and np.all(theta[:npar] > 0.0)
+                            and np.all(np.isfinite(Z))):
+                        out[i] = failed(i, N.InvalidParameterError(
+                            f"model {i}: a hyperparameter left (0, inf) or an inducing input is not finite"))
+                        continue
+                    eng.pack(slot[i], theta, Z)
+                    call.append(i)
+                if call:
+                    info = eng.elbo_grad([slot[i] for i in call])
+                    for i in call:
+                        if info[slot[i]].any():
+                            out[i] = failed(i, eng.not_pd(info[slot[i]]))
+                        else:
+                            out[i] = models[i].grads_to_unconstrained(variables[i], *eng.result(slot[i]))
+                for i in active:
+                    steppers[i].tell(*out[i])
+                active = [i for i in active if not steppers[i].done]
+        results = []
+        for v, st in zip(variables, steppers):
+            res = st.result()
+            _unpack(v, res.x)
+            results.append(res)
+        return results
+
     def minimize_stream(self, models: Sequence, width: int, method: str = "L-BFGS-B",
                         device: Optional[int] = None, predict_train: bool = False,
                         engine=None, groups: int = 1,

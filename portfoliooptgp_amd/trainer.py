@@ -8,6 +8,8 @@
   previous optimum and earlier best models alias the mutated kernels).
 * ``ModelTrainer.train_svgp_model`` — test_scripts/GPR.py:118-138: the same sweep with one SVGP per
   kernel (Gaussian(1e-4) frozen, inducing points X[:20]), fitted by ``Scipy().minimize_svgp_batch``.
+* ``ModelTrainer.train_sgpr_model`` — the same sweep over the SGPR cell of test_scripts/SVGP.py:393-400
+  (noise 1.0 and Z trainable, inducing points on a linspace grid), fitted by ``Scipy().minimize_sgpr_batch``.
 * ``Predictor`` — GPR/predictor.py:4-51 (predict_single; predict_combined and
   upsample_predictions as host post-processing).
 * ``MultiInputTrainer`` — Multi-Input_GPR/models/model_trainer.py:17-72 (train_model,
@@ -81,6 +83,33 @@ class ModelTrainer:
         self.last_results = Scipy().minimize_svgp_batch(models, (X_tf, Y_tf), options=dict(maxiter=maxiter))
         self.last_models = models
         preds = M.predict_f_svgp_batch(models, [X_tf] * len(models))
+        best_kernel, best_mse, best_model = None, float("inf"), None
+        for kernel, model, (mean, _) in zip(self.kernel_combinations, models, preds):
+            mse = mean_squared_error(Y_tf, _np(mean))
+            if mse < best_mse:
+                best_mse, best_kernel, best_model = mse, kernel, model
+        return best_kernel, best_mse, best_model
+
+    def train_sgpr_model(self, X_tf, Y_tf, n_inducing: int = 10, maxiter: int = 100):
+        """The sparse sweep beside train_svgp_model, over the reference's SGPR cell
+        (test_scripts/SVGP.py:393-400): per kernel an SGPR((X, Y), kernel, inducing_variable=Z0) with
+        GPflow's defaults (noise variance 1.0 trainable, Z trainable). For one input column Z0 is the
+        cell's layout, ``np.linspace(X.min(), X.max(), n_inducing)[:, None]``; for several, the rows of X
+        at the indices ``np.linspace(0, N − 1, n_inducing).round()``. L-BFGS-B maxiter=100, predict_f
+        at the training X, the minimum training MSE wins (strict ``<``, first wins). The kernel fits
+        run in one lock-step batch, one device call per round."""
+        Xn = _np(X_tf)
+        Xn = Xn.reshape(Xn.shape[0], -1)
+        if Xn.shape[1] == 1:
+            Z0 = np.linspace(Xn.min(), Xn.max(), n_inducing)[:, None]
+        else:
+            Z0 = Xn[np.linspace(0, Xn.shape[0] - 1, n_inducing).round().astype(int)]
+        models = [M.SGPR((X_tf, Y_tf), kernel, inducing_variable=np.array(Z0, dtype=np.float64),
+                         device=self.device)
+                  for kernel in self.kernel_combinations]
+        self.last_results = Scipy().minimize_sgpr_batch(models, options=dict(maxiter=maxiter))
+        self.last_models = models
+        preds = M.predict_f_sgpr_batch(models, [X_tf] * len(models))
         best_kernel, best_mse, best_model = None, float("inf"), None
         for kernel, model, (mean, _) in zip(self.kernel_combinations, models, preds):
             mse = mean_squared_error(Y_tf, _np(mean))
