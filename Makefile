@@ -17,7 +17,7 @@ $(LOOPMOD): $(CSRC)/gpx_lbfgsb_host.cpp
 	g++ -O2 -std=c++17 -fPIC -shared -Wall -Wextra -Wno-missing-field-initializers -Wno-cast-function-type \
 	  -I$(PYINC) $< -o $@
 
-$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/gpx_internal.h $(CSRC)/gpx_host.h $(CSRC)/gpx_kfun.h $(CSRC)/gpx_mean.h $(CSRC)/gpx_leaf.h $(CSRC)/gpx_b16core.h $(CSRC)/gpx_kfun_ard.h $(CSRC)/gpx_quad.h $(CSRC)/gpx_reduce.h include/gpx.h
+$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/gpx_internal.h $(CSRC)/gpx_host.h $(CSRC)/gpx_kfun.h $(CSRC)/gpx_mean.h $(CSRC)/gpx_leaf.h $(CSRC)/gpx_b16core.h $(CSRC)/gpx_kfun_ard.h $(CSRC)/gpx_kfun_coreg.h $(CSRC)/gpx_quad.h $(CSRC)/gpx_reduce.h include/gpx.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # host helpers of the L-BFGS-B driver: plain gcc, libm calls as Python's math module makes them
@@ -25,7 +25,7 @@ $(CSRC)/gpx_host_math.o: $(CSRC)/gpx_host_math.c include/gpx.h
 	gcc -O2 -fno-builtin -fno-fast-math -fPIC -std=c11 -Wall -c $< -o $@
 
 # the library's objects (the phases library below swaps in its three instrumented ones)
-OBJS := $(addprefix $(CSRC)/,gpx_kernels.o gpx_api.o gpx_knobs.o gpx_dense.o gpx_route.o gpx_eval.o gpx_predict.o gpx_ard.o \
+OBJS := $(addprefix $(CSRC)/,gpx_kernels.o gpx_api.o gpx_knobs.o gpx_dense.o gpx_route.o gpx_eval.o gpx_predict.o gpx_ard.o gpx_coregion.o \
   gpx_band.o gpx_band16.o gpx_bcr.o gpx_mean.o gpx_svgp_kernels.o gpx_svgp_lik_kernels.o gpx_svgp.o gpx_svgp_small.o gpx_sgpr.o gpx_sgpr_small.o gpx_vgp_kernels.o gpx_vgp.o gpx_host_math.o)
 $(OBJS): $(CSRC)/gpx_knobs.h
 
@@ -65,7 +65,7 @@ HOBJ := $(patsubst $(CSRC)/%.hip,build/asan/%.o,$(HSRC))
 $(HOBJ) build/asan/host_harness.o: $(CSRC)/gpx_knobs.h
 HSAN := -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-sanitize-recover=undefined \
   -Xarch_host -fno-omit-frame-pointer -g -O1
-build/asan/%.o: $(CSRC)/%.hip $(CSRC)/gpx_internal.h $(CSRC)/gpx_host.h $(CSRC)/gpx_kfun.h $(CSRC)/gpx_mean.h $(CSRC)/gpx_leaf.h $(CSRC)/gpx_b16core.h $(CSRC)/gpx_kfun_ard.h $(CSRC)/gpx_quad.h $(CSRC)/gpx_reduce.h include/gpx.h
+build/asan/%.o: $(CSRC)/%.hip $(CSRC)/gpx_internal.h $(CSRC)/gpx_host.h $(CSRC)/gpx_kfun.h $(CSRC)/gpx_mean.h $(CSRC)/gpx_leaf.h $(CSRC)/gpx_b16core.h $(CSRC)/gpx_kfun_ard.h $(CSRC)/gpx_kfun_coreg.h $(CSRC)/gpx_quad.h $(CSRC)/gpx_reduce.h include/gpx.h
 	@mkdir -p build/asan
 	$(HIPCC) --offload-arch=$(ARCH) -std=c++17 -fPIC $(HSAN) -c $< -o $@
 build/asan/gpx_host_math.o: $(CSRC)/gpx_host_math.c include/gpx.h

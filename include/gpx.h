@@ -40,11 +40,15 @@
  *      RationalQuadratic                         : [alpha, lengthscales, variance]
  *      Periodic(SquaredExponential)              : [base.lengthscales, base.variance, period]
  *      Linear                                    : [variance]
+ *      Coregion (GPX_COREGION)                   : [W row-major (P*R), kappa (P)]
  *    With GPX_TERM_ARD in a stationary term's kind (one lengthscale per active dimension, GPflow's
  *    vector `lengthscales`; see gpx_term below) its dim_count lengthscales take the scalar's place:
  *      SE/Matern/Exponential | GPX_TERM_ARD      : [l_0 .. l_{dim_count-1}, variance]
  *      RationalQuadratic | GPX_TERM_ARD          : [alpha, l_0 .. l_{dim_count-1}, variance]
  *    Such problems always take the dense path, in the same batches and calls as the others.
+ *    Signed slots: the W entries of a Coregion term may be any finite value (negative and zero
+ *    too). Every other kernel parameter, kappa included, and the noise variance must be finite
+ *    and > 0; anything else is GPX_BAD_ARG.
  *  - Return codes: GPX_OK, GPX_NOT_PD (some problem's K+σn²I is not positive definite; its
  *    info[b] holds the 1-based index of the first failing pivot, like LAPACK potrf),
  *    GPX_BAD_ARG, GPX_HIP_ERROR. No C++ exception crosses this boundary.
@@ -84,7 +88,8 @@ typedef enum {
   GPX_EXPONENTIAL = 5, /* σ² exp(-r/2)                          gpflow.kernels.Exponential */
   GPX_RQ = 6,          /* σ² (1+r²/(2α))^(-α)                   gpflow.kernels.RationalQuadratic */
   GPX_PERIODIC_SE = 7, /* σ² exp(-½Σ(sin(πΔ/p)/ℓ)²)             gpflow.kernels.Periodic(SE) */
-  GPX_LINEAR = 8       /* σ² x·x'                               gpflow.kernels.Linear */
+  GPX_LINEAR = 8,      /* σ² x·x'                               gpflow.kernels.Linear */
+  GPX_COREGION = 9     /* B[a, b], B = W Wᵀ + diag(κ)           gpflow.kernels.Coregion */
 } gpx_term_kind;
 
 typedef enum { GPX_SUM = 0, GPX_PRODUCT = 1 } gpx_combine;
@@ -106,6 +111,28 @@ typedef enum { GPX_SUM = 0, GPX_PRODUCT = 1 } gpx_combine;
 #define GPX_TERM_ARD 0x100
 #define GPX_TERM_KIND_MASK 0xff
 
+/*
+ * Coregion (gpflow.kernels.Coregion, the intrinsic coregionalisation model): a term of kind
+ * GPX_COREGION acts on exactly one input column (dim_count == 1) that holds each row's output
+ * index a in [0, P). K(x, x') = B[a, a'] with B = W Wᵀ + diag(kappa), W of shape [P, R] (signed)
+ * and kappa of shape [P] (> 0). P (output_dim) and R (rank) sit in gpx_kernel_spec.reserved as
+ * P | R << 8; the term's theta slots are [W row-major (P*R), kappa (P)] at param_offset, and grad
+ * carries dlogML/dW_pr and dlogML/dkappa_p in the same columns. The index is read as an integer
+ * and clamped to [0, P - 1] on the device: callers validate it (the Python surface refuses any
+ * value that is not an exact integer in [0, P)).
+ * A spec holds at most one Coregion term, alone or as one factor of a GPX_PRODUCT spec with any
+ * other term kinds (GPX_TERM_ARD ones included). Such a spec always takes the dense route
+ * (gpx_batch_band_width / _band_class report -1; band storage runs it on the fallback slots),
+ * leaves the theta row's last column free like an ARD spec (n_params + 1 <= GPX_THETA_STRIDE - 1),
+ * and is accepted by the gpx_batch_* entry points only (gpx_svgp / gpx_sgpr / gpx_vgp and their
+ * *_small_* creators refuse it). Refused with GPX_BAD_ARG and these gpx_last_error texts:
+ *   "a Coregion term acts on exactly one input column (dim_count == 1)"
+ *   "a Coregion spec needs P >= 1 and R >= 1 in reserved (P | R << 8)"
+ *   "a spec may hold one Coregion term"
+ *   "a Coregion term is valid alone or in a GPX_PRODUCT spec, not in a GPX_SUM"
+ *   "a Coregion spec may use GPX_THETA_STRIDE - 1 columns of the theta row (kernel parameters + noise)"
+ *   "reserved must be 0 in a spec without a Coregion term"
+ */
 typedef struct {
   int32_t kind;         /* gpx_term_kind, optionally | GPX_TERM_ARD */
   int32_t dim_start;    /* active_dims = slice(dim_start, dim_start + dim_count) */
@@ -117,7 +144,7 @@ typedef struct {
   int32_t n_terms;      /* 1..GPX_MAX_TERMS */
   int32_t combine;      /* gpx_combine (ignored when n_terms == 1) */
   int32_t n_params;     /* kernel parameters; the noise variance sits at theta[n_params] */
-  int32_t reserved;
+  int32_t reserved;     /* P | R << 8 of the spec's Coregion term; 0 without one */
   gpx_term terms[GPX_MAX_TERMS];
 } gpx_kernel_spec;
 
@@ -141,6 +168,12 @@ const char* gpx_version(void);
 int gpx_create(int device, gpx_ctx** out);
 int gpx_destroy(gpx_ctx* ctx);
 const char* gpx_last_error(const gpx_ctx* ctx);
+
+/* The signed theta slots of a spec for inputs of D columns: bit p of *mask_out is set when slot p
+ * may hold any finite value (the W entries of a Coregion term); every other kernel parameter and
+ * the noise variance must be finite and > 0. Pure host logic, no device needed. GPX_BAD_ARG for a
+ * spec that gpx_batch_create would refuse. */
+int gpx_spec_signed_mask(const gpx_kernel_spec* spec, int D, uint32_t* mask_out);
 
 /*
  * A batch of B independent GPR problems (the per-asset / per-kernel fits of

@@ -18,6 +18,7 @@ GPX_MAX_DIM = 16
 
 (GPX_SE, GPX_MATERN12, GPX_MATERN32, GPX_MATERN52, GPX_EXPONENTIAL, GPX_RQ, GPX_PERIODIC_SE,
  GPX_LINEAR) = range(1, 9)
+GPX_COREGION = 9  # gpflow.kernels.Coregion; P | R << 8 in gpx_kernel_spec.reserved (include/gpx.h)
 # flag bit of gpx_term.kind: ARD, one lengthscale per active dim (include/gpx.h)
 GPX_TERM_ARD, GPX_TERM_KIND_MASK = 0x100, 0xFF
 GPX_SUM, GPX_PRODUCT = 0, 1
@@ -55,6 +56,7 @@ EXPORTED_SYMBOLS = (
     "gpx_vgp_create", "gpx_vgp_destroy", "gpx_vgp_elbo_grad", "gpx_vgp_predict",
     "gpx_host_theta_rows", "gpx_host_loss_grad_u",
     "gpx_batch_set_mean", "gpx_host_theta_rows_t", "gpx_host_loss_grad_u_t",
+    "gpx_spec_signed_mask",
 )
 
 
@@ -204,6 +206,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.gpx_batch_deferred_wait.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
         lib.gpx_batch_deferred_rows.restype = c_int
         lib.gpx_batch_deferred_rows.argtypes = [c_void_p, c_void_p, c_int]
+        lib.gpx_spec_signed_mask.restype = c_int
+        lib.gpx_spec_signed_mask.argtypes = [c_void_p, c_int, c_void_p]
         lib.gpx_batch_band_class.restype = c_int
         lib.gpx_batch_band_class.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p]
         lib.gpx_batch_wave_trace.restype = c_int

@@ -129,17 +129,23 @@ void factor(const Run& r) {
   ba.X = bt->X; ba.sX = (long long)bt->Nmax * bt->D; ba.X2 = bt->X; ba.sX2 = ba.sX; ba.D = bt->D;
   ba.m2 = 0; ba.out = bt->K; ba.sOut = mat_stride(bt); ba.ldo = bt->Np; ba.rows = ba.cols = bt->Np;
   ba.symmetric = 1;
-  build_range(ba, r.na, r.n_ard, r.s);
+  build_range(ba, r.na, r.n_ard, r.n_cg, r.s);
   chol_inv(r, 0, bt->Np);
 }
 
-// the isotropic problems of a range by build_kernel, its trailing ARD ones by build_ard_kernel
-void build_range(const BuildArgs& a, int na, int n_ard, hipStream_t s) {
+// the isotropic problems of a range by build_kernel, its trailing ARD ones by build_ard_kernel, the
+// Coregion ones behind those by build_coreg_kernel
+void build_range(const BuildArgs& a, int na, int n_ard, int n_cg, hipStream_t s) {
   if (na > n_ard) launch_build(a, na - n_ard, s);
-  if (n_ard > 0) {
+  if (n_ard > n_cg) {
     BuildArgs b = a;
     b.active = a.active + (na - n_ard);
-    launch_build_ard(b, n_ard, s);
+    launch_build_ard(b, n_ard - n_cg, s);
+  }
+  if (n_cg > 0) {
+    BuildArgs b = a;
+    b.active = a.active + (na - n_cg);
+    launch_build_coreg(b, n_cg, s);
   }
 }
 
@@ -177,12 +183,20 @@ void contract(const Run& r, int max_terms, hipEvent_t ev0, hipEvent_t ev1) {
     gemm(ri, g, max_terms <= 1 ? EPI_CONTRACT1 : max_terms == 2 ? EPI_CONTRACT2 : EPI_CONTRACT, true, false);
     g.ev_start = g.ev_stop = nullptr;  // (a mixed call's contraction time: its isotropic launch)
   }
-  if (r.n_ard > 0) {
-    // the ARD problems (the range's last n_ard): the θ-indexed epilogue, sized by their own specs
+  if (r.n_ard > r.n_cg) {
+    // the ARD problems (behind the isotropic ones): the θ-indexed epilogue, sized by their own specs
     Run ra = r;
     ra.d_act = r.d_act + n_iso;
-    ra.na = r.n_ard;
+    ra.na = r.n_ard - r.n_cg;
     gemm(ra, g, r.ard_terms <= 2 ? EPI_CONTRACT_ARD2 : EPI_CONTRACT_ARD, true, false);
+    g.ev_start = g.ev_stop = nullptr;
+  }
+  if (r.n_cg > 0) {
+    // the Coregion problems (the range's last n_cg): their own epilogue, one instance per tile size
+    Run rc = r;
+    rc.d_act = r.d_act + (r.na - r.n_cg);
+    rc.na = r.n_cg;
+    gemm(rc, g, EPI_CONTRACT_COREG, true, false);
   }
 }
 

@@ -478,10 +478,11 @@ static int check_active_theta(gpx_batch* bt, int n_active, const int32_t* active
   for (int i = 0; i < n_active; ++i) {
     const int b = active[i];
     const int np = bt->specs[b].n_params;
+    const unsigned sgn = signed_slot_mask(bt->specs[b]);  // (a Coregion term's W: any finite value)
     for (int p = 0; p <= np; ++p) {
       const double v = theta[(size_t)b * GPX_THETA_STRIDE + p];
-      if (!(v > 0.0) || !std::isfinite(v))
-        return fail(ctx, GPX_BAD_ARG, "theta must be finite and > 0 (constrained space)");
+      if ((!(v > 0.0) && !((sgn >> p) & 1u)) || !std::isfinite(v))
+        return fail(ctx, GPX_BAD_ARG, "theta must be finite and > 0 (constrained space; a Coregion W: finite)");
     }
     // (a mean function's coefficients, behind the noise: any finite value, zero and negative too)
     for (int p = np + 1, e = np + 1 + mean_ncoef(bt, b); p < e; ++p)
@@ -1062,7 +1063,7 @@ int submit_all_shadow(SubmitCall& c) {
 bool small_direct_call(const SubmitCall& c) {
   // (not for a batch with a mean function: its gradient kernel follows the fused launch, whose
   // polled flag would tell the host to read the results before that kernel has written its columns)
-  // (nor with ARD problems: they take the launch chain below)
+  // (nor with ARD or Coregion problems, n_ard counts both: they take the launch chain below)
   return knob_on(Knob::SmallDirect) && small64_on(c.bt) && c.rt.n_dense == c.n_active && !c.shadow_async &&
          c.rt.shadow_ids.empty() && c.bt->n_mean == 0 && c.rt.n_ard == 0;
 }
@@ -1105,7 +1106,8 @@ int submit_dense(SubmitCall& c, gpx_batch::PendingEval& pe) {
   hipStream_t s = c.s;
   const int n_dense = c.rt.n_dense;
   if (n_dense == 0) return GPX_OK;
-  const int n_ard = c.rt.n_ard, n_iso = n_dense - n_ard;  // (the ARD problems: the last n_ard)
+  // (the ARD and Coregion problems: the last n_ard, the Coregion ones the last n_cg of those)
+  const int n_ard = c.rt.n_ard, n_iso = n_dense - n_ard, n_cg = c.rt.n_cg;
   if (small64_on(bt)) {
     // Np = 64: the whole evaluation of every dense problem in one launch
     if (n_iso > 0) small64_eval(Run{bt, bt->d_active, n_iso, s}, true);
@@ -1114,7 +1116,8 @@ int submit_dense(SubmitCall& c, gpx_batch::PendingEval& pe) {
       // with the ARD build and epilogue — by its spec, whatever else the call holds
       Run ra{bt, bt->d_active + n_iso, n_ard, s};
       ra.n_ard = n_ard;
-      ra.ard_terms = c.max_terms(n_iso, n_dense);
+      ra.n_cg = n_cg;
+      ra.ard_terms = c.max_terms(n_iso, n_dense - n_cg);
       factor(ra);
       alpha_solve(ra);
       contract(ra, 1);
@@ -1142,6 +1145,7 @@ int submit_dense(SubmitCall& c, gpx_batch::PendingEval& pe) {
     const int cnt = n_dense / ng + (g < n_dense % ng ? 1 : 0);
     runs[g] = Run{bt, bt->d_active + start, cnt, ng == 1 ? s : bt->workers[g], ng == 1, &next_event};
     runs[g].n_ard = std::max(0, start + cnt - std::max(start, n_iso));
+    runs[g].n_cg = std::max(0, start + cnt - std::max(start, n_dense - n_cg));
     start += cnt;
   }
   if (ng > 1) {
@@ -1178,7 +1182,8 @@ int submit_dense(SubmitCall& c, gpx_batch::PendingEval& pe) {
   const bool prio = knob_on(Knob::ContractPriority);
   Run cr{bt, bt->d_active, n_dense, s};
   cr.n_ard = n_ard;
-  cr.ard_terms = c.max_terms(n_iso, n_dense);
+  cr.n_cg = n_cg;
+  cr.ard_terms = c.max_terms(n_iso, n_dense - n_cg);
   if (prio) {
     if (!bt->hp) {
       int lo = 0, hi = 0;

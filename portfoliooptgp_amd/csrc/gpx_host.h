@@ -259,6 +259,11 @@ struct Run {
   // them behind the isotropic ones), built and contracted by the ARD kernels
   int n_ard = 0;
   int ard_terms = 1;  // the most terms of an ARD problem's spec (contract's max_terms: the isotropic ones')
+  // ... and the last n_cg of those n_ard have a Coregion term (coreg_spec; ordered behind the ARD
+  // ones): built and contracted by the Coregion kernels. n_ard counts them too — the range's
+  // whole non-isotropic tail — so what excludes ARD problems (the fused small-size launch)
+  // excludes them alike.
+  int n_cg = 0;
 };
 
 struct PhaseTimer {
@@ -315,7 +320,8 @@ struct Route {
   std::vector<int32_t> order;
   std::vector<int32_t> shadow_ids;
   int n_dense = 0, n_band = 0, n_fused = 0, n16 = 0, n_fused1 = 0, pband = 0;
-  int n_ard = 0;  // the dense problems whose spec has an ARD term: the last n_ard of [0, n_dense)
+  int n_ard = 0;  // the dense problems whose spec has an ARD or Coregion term: the last n_ard of [0, n_dense)
+  int n_cg = 0;   // ... of which the last n_cg have a Coregion term
   int n_g16 = 0, g16_q[kBand16MaxQ] = {}, g16_n[kBand16MaxQ] = {};
   bool b16_p2 = false;
 };
@@ -333,8 +339,17 @@ bool ard_spec(const gpx_kernel_spec& sp);     // some term carries GPX_TERM_ARD:
 int term_param_count(const gpx_term& tm);
 // why a spec cannot be taken for inputs of D columns (gpx_last_error's text), or null
 const char* spec_error(const gpx_kernel_spec& sp, int D);
-// K / cross-covariance build of a range whose last n_ard problems are ARD specs
-void build_range(const BuildArgs& a, int na, int n_ard, hipStream_t s);
+// what gpx_svgp / gpx_sgpr / gpx_vgp and their *_small_* creators answer to such a spec
+constexpr const char* kCoregBatchOnlyMsg = "Coregion terms (GPX_COREGION) are served by the gpx_batch_* entry points only";
+bool coreg_spec(const gpx_kernel_spec& sp);   // some term is GPX_COREGION: the dense Coregion kernels
+// a dense range's class order: 0 isotropic, 1 ARD, 2 Coregion (an ARD partner does not change that)
+int dense_class(const gpx_kernel_spec& sp);
+// bit p set: θ slot p of the spec is signed (a Coregion term's W entries: any finite value);
+// every other kernel parameter and the noise variance must be finite and > 0
+unsigned signed_slot_mask(const gpx_kernel_spec& sp);
+// K / cross-covariance build of a range whose last n_ard problems are ARD or Coregion specs, the
+// last n_cg of those Coregion ones
+void build_range(const BuildArgs& a, int na, int n_ard, int n_cg, hipStream_t s);
 enum RouteKind { kRouteDense, kRouteShadow, kRouteBand, kRouteFused, kRouteBand16 };
 RouteLimits route_limits(const gpx_batch* bt);
 RouteKind route_one(const gpx_batch* bt, int b, const double* theta_row, const RouteLimits& L, int& w);

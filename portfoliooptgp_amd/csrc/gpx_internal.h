@@ -45,8 +45,10 @@ enum : int { TRI_KMAX_I = 1, TRI_KMAX_J = 2, TRI_KMIN_J = 4, TRI_KMIN_I = 8 };
 // n_terms == 1): a quarter of the derivative registers, no spills in the epilogue.
 // EPI_CONTRACT_ARD2 / _ARD: the contraction of specs with ARD terms (gpx_kfun_ard.h), at most two
 // terms / up to GPX_MAX_TERMS; the lower-tile WᵀW launch only.
+// EPI_CONTRACT_COREG: the contraction of specs with a Coregion term (gpx_kfun_coreg.h); the
+// lower-tile WᵀW launch only.
 enum : int { EPI_STORE = 0, EPI_CONTRACT = 1, EPI_COLSUMSQ = 2, EPI_CONTRACT1 = 3, EPI_CONTRACT2 = 4,
-             EPI_CONTRACT_ARD2 = 5, EPI_CONTRACT_ARD = 6 };
+             EPI_CONTRACT_ARD2 = 5, EPI_CONTRACT_ARD = 6, EPI_CONTRACT_COREG = 7 };
 // tile enumeration for rectangular launches (see gemm_kernel)
 enum : int { ORDER_ROW_ASC = 0, ORDER_COL_DESC = 1, ORDER_ROW_DESC = 2, ORDER_COL_ASC = 3 };
 
@@ -288,6 +290,7 @@ void launch_band_train_pred(const TrainPredArgs& a, int n_active, int Np, hipStr
 
 void launch_build(const BuildArgs& a, int n_active, hipStream_t s);
 void launch_build_ard(const BuildArgs& a, int n_active, hipStream_t s);      // specs with ARD terms (gpx_ard.hip)
+void launch_build_coreg(const BuildArgs& a, int n_active, hipStream_t s);    // specs with a Coregion term (gpx_coregion.hip)
 void launch_leaf(const LeafArgs& a, int n_active, hipStream_t s);
 void launch_leaf128(const LeafArgs& a, int n_active, hipStream_t s);  // 128x128 block, fused
 void launch_gemm(const GemmArgs& a, int epi, bool ta, bool tb, int n_active, hipStream_t s);
@@ -297,6 +300,7 @@ void launch_reduce(const ReduceArgs& a, int n_active, hipStream_t s);
 void launch_train_pred(const TrainPredArgs& a, int n_active, int Np, hipStream_t s);
 void launch_predvar(const PredVarArgs& a, int n_active, hipStream_t s);
 void launch_predvar_ard(const PredVarArgs& a, int n_active, hipStream_t s);  // specs with ARD terms (gpx_ard.hip)
+void launch_predvar_coreg(const PredVarArgs& a, int n_active, hipStream_t s);  // specs with a Coregion term (gpx_coregion.hip)
 int gemm_tile(const GemmArgs& a, int n_active);  // tile edge the launcher will use (64 or 128)
 // The GEMM stages operands with buffer loads: a per-K-tile base plus a 32-bit per-lane byte
 // offset, inside a 0x7fffffff-byte buffer window. The farthest element a tile reads is

@@ -17,6 +17,7 @@
 #include "gpx_internal.h"
 #include "gpx_leaf.h"
 #include "gpx_kfun_ard.h"
+#include "gpx_kfun_coreg.h"
 
 namespace gpx {
 
@@ -478,7 +479,9 @@ void gemm_kernel(GemmArgs a) {
   constexpr int NLD = BM * BK / 2 / 256;  // double2 chunks per thread per operand
   constexpr int kMainLds = 2 * 2 * BK * S;
   constexpr bool kArdEpi = EPI == EPI_CONTRACT_ARD2 || EPI == EPI_CONTRACT_ARD;
-  constexpr bool kContractEpi = EPI == EPI_CONTRACT || EPI == EPI_CONTRACT1 || EPI == EPI_CONTRACT2 || kArdEpi;
+  constexpr bool kCoregEpi = EPI == EPI_CONTRACT_COREG;
+  constexpr bool kContractEpi = EPI == EPI_CONTRACT || EPI == EPI_CONTRACT1 || EPI == EPI_CONTRACT2 || kArdEpi ||
+                                kCoregEpi;
   constexpr int kEpiLds = kContractEpi
       ? 4 * 16 * WT + 2 * BM * GPX_MAX_DIM + 2 * BM + GPX_THETA_STRIDE + 64 : 0;
   __shared__ __attribute__((aligned(16))) double smem[kMainLds > kEpiLds ? kMainLds : kEpiLds];
@@ -819,6 +822,12 @@ void gemm_kernel(GemmArgs a) {
         a.X + (long long)b * a.sX, a.vec + (long long)b * a.sVec, a.theta + b * GPX_THETA_STRIDE, a.specs + b,
         a.D, a.nvalid[b], i0, j0, acc, smem,
         a.partial + (long long)b * a.sPartial + (long long)tile * GPX_THETA_STRIDE);
+  } else if constexpr (kCoregEpi) {
+    // specs with a Coregion term (gpx_kfun_coreg.h): θ-indexed sums, the W / κ slots among them
+    cg_contract_tile<BM, MT>(
+        a.X + (long long)b * a.sX, a.vec + (long long)b * a.sVec, a.theta + b * GPX_THETA_STRIDE, a.specs + b,
+        a.D, a.nvalid[b], i0, j0, acc, smem,
+        a.partial + (long long)b * a.sPartial + (long long)tile * GPX_THETA_STRIDE);
   } else {  // EPI_COLSUMSQ
     double* scol = smem;  // [2][BN]
     __syncthreads();
@@ -881,8 +890,8 @@ static void launch_gemm_t(const GemmArgs& a0, bool ta, bool tb, int n_active, hi
   else hipLaunchKernelGGL((gemm_kernel<BM, true, true, EPI>), grid, dim3(256), 0, s, a);
 }
 
-// the ARD contraction (K⁻¹ = WᵀW: opA transposed, opB not): the tile size by the shape only, as the
-// isotropic contraction's
+// the ARD and Coregion contractions (K⁻¹ = WᵀW: opA transposed, opB not): the tile size by the shape
+// only, as the isotropic contraction's
 static void launch_gemm_ard(const GemmArgs& a0, int epi, int n_active, hipStream_t s) {
   GemmArgs a = a0;
   a.n_active = n_active;
@@ -892,9 +901,11 @@ static void launch_gemm_ard(const GemmArgs& a0, int epi, int n_active, hipStream
   const int q = n_active / 8, r = n_active % 8;
   dim3 grid(8 * (q * ntiles + (r * ntiles + 7) / 8));
   auto k = bm == 128 ? (epi == EPI_CONTRACT_ARD2 ? gemm_kernel<128, true, false, EPI_CONTRACT_ARD2>
-                                                 : gemm_kernel<128, true, false, EPI_CONTRACT_ARD>)
+                        : epi == EPI_CONTRACT_ARD ? gemm_kernel<128, true, false, EPI_CONTRACT_ARD>
+                                                  : gemm_kernel<128, true, false, EPI_CONTRACT_COREG>)
                      : (epi == EPI_CONTRACT_ARD2 ? gemm_kernel<64, true, false, EPI_CONTRACT_ARD2>
-                                                 : gemm_kernel<64, true, false, EPI_CONTRACT_ARD>);
+                        : epi == EPI_CONTRACT_ARD ? gemm_kernel<64, true, false, EPI_CONTRACT_ARD>
+                                                  : gemm_kernel<64, true, false, EPI_CONTRACT_COREG>);
   if (a.ev_start) hipExtLaunchKernelGGL(k, grid, dim3(256), 0, s, a.ev_start, a.ev_stop, 0, a);
   else hipLaunchKernelGGL(k, grid, dim3(256), 0, s, a);
 }
@@ -907,9 +918,9 @@ void launch_gemm(const GemmArgs& a, int epi, bool ta, bool tb, int n_active, hip
             a.lda, a.ldb, kGemmMaxLd);
     abort();
   }
-  if (epi == EPI_CONTRACT_ARD2 || epi == EPI_CONTRACT_ARD) {
+  if (epi == EPI_CONTRACT_ARD2 || epi == EPI_CONTRACT_ARD || epi == EPI_CONTRACT_COREG) {
     if (!ta || tb || !a.lower_only) {
-      fprintf(stderr, "gpx: the ARD contraction is the lower-tile WᵀW launch only\n");
+      fprintf(stderr, "gpx: the ARD / Coregion contraction is the lower-tile WᵀW launch only\n");
       abort();
     }
     return launch_gemm_ard(a, epi, n_active, s);

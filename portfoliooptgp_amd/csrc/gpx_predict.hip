@@ -134,13 +134,17 @@ static int predict_impl(gpx_batch* bt, int n_active, const int32_t* active, cons
     if (std::find(band_cached.begin(), band_cached.end(), active[i]) == band_cached.end())
       order.push_back(active[i]);
   const int n_dense = (int)order.size();
-  // specs with ARD terms last in each list: their K builds and k** are the ARD kernels'
-  const auto iso_first = [&](int32_t b) { return !ard_spec(bt->specs[b]); };
+  // specs with ARD terms last in each list, those with a Coregion term behind them: their K builds
+  // and k** are the ARD / Coregion kernels' (n_ard counts both, as Run::n_ard)
+  const auto iso_first = [&](int32_t b) { return dense_class(bt->specs[b]) == 0; };
+  const auto not_cg = [&](int32_t b) { return dense_class(bt->specs[b]) != 2; };
   const int n_ard = (int)(order.end() - std::stable_partition(order.begin(), order.end(), iso_first));
+  const int n_cg = (int)(order.end() - std::stable_partition(order.end() - n_ard, order.end(), not_cg));
   order.insert(order.end(), band_cached.begin(), band_cached.end());
   if (!refac.empty()) {
     const int r_ard = (int)(refac.end() - std::stable_partition(refac.begin(), refac.end(), iso_first));
     const int r_iso = (int)refac.size() - r_ard;
+    const int r_cg = (int)(refac.end() - std::stable_partition(refac.end() - r_ard, refac.end(), not_cg));
     HIPX(ctx, hipMemcpyAsync(bt->d_active, refac.data(), sizeof(int) * refac.size(),
                              hipMemcpyHostToDevice, s));
     if (bt->n_mean > 0) {  // the re-factorised problems' α is solved against y − m(X; β) at this β
@@ -152,12 +156,14 @@ static int predict_impl(gpx_batch* bt, int n_active, const int32_t* active, cons
       if (r_ard > 0) {  // (an ARD problem of these sizes: the launch chain, as its evaluations)
         Run ra{bt, bt->d_active + r_iso, r_ard, s};
         ra.n_ard = r_ard;
+        ra.n_cg = r_cg;
         factor(ra);
         alpha_solve(ra);
       }
     } else {
       Run rr{bt, bt->d_active, (int)refac.size(), s};
       rr.n_ard = r_ard;
+      rr.n_cg = r_cg;
       factor(rr);
       alpha_solve(rr);
     }
@@ -203,7 +209,7 @@ static int predict_impl(gpx_batch* bt, int n_active, const int32_t* active, cons
   ba.X = bt->X; ba.sX = (long long)bt->Nmax * bt->D; ba.X2 = Xnew; ba.sX2 = (long long)M * bt->D;
   ba.D = bt->D; ba.m2 = M; ba.out = kxs; ba.sOut = skx; ba.ldo = Mp; ba.rows = Np; ba.cols = Mp;
   ba.symmetric = 0;
-  build_range(ba, n_active, n_ard, s);
+  build_range(ba, n_active, n_ard, n_cg, s);
   // mean = Kxsᵀ α
   TrmvArgs t{};
   t.active = bt->d_active; t.Wm = kxs; t.sW = skx; t.ld = Mp; t.x = bt->alpha; t.sx = Np;
@@ -229,7 +235,7 @@ static int predict_impl(gpx_batch* bt, int n_active, const int32_t* active, cons
     BuildArgs kb = ba;
     kb.X = Xnew; kb.sX = (long long)M * bt->D; kb.rows_valid = M; kb.out = bt->covw; kb.sOut = scv;
     kb.ldo = Mp; kb.rows = Mp; kb.cols = Mp;
-    build_range(kb, n_active, n_ard, s);
+    build_range(kb, n_active, n_ard, n_cg, s);
     const Run rr{bt, bt->d_active, n_active, s};
     GemmArgs ga = gemm_args(bt->W, Np, kxs, Mp, abuf, Mp, 0, Np, Mp, Np, TRI_KMAX_I, 0, 1.0, 0.0);
     ga.sA = mat_stride(bt); ga.sB = skx; ga.sC = skx;
@@ -263,9 +269,13 @@ static int predict_impl(gpx_batch* bt, int n_active, const int32_t* active, cons
   pv.specs = bt->d_specs; pv.theta = bt->d_theta; pv.M = M; pv.add_noise = add_noise;
   pv.var = var; pv.sVar = M;
   if (n_active > n_ard) launch_predvar(pv, n_active - n_ard, s);
-  if (n_ard > 0) {
+  if (n_ard > n_cg) {
     pv.active = bt->d_active + (n_active - n_ard);
-    launch_predvar_ard(pv, n_ard, s);
+    launch_predvar_ard(pv, n_ard - n_cg, s);
+  }
+  if (n_cg > 0) {
+    pv.active = bt->d_active + (n_active - n_cg);
+    launch_predvar_coreg(pv, n_cg, s);
   }
   }
   }

@@ -292,10 +292,14 @@ void route_call(gpx_batch* bt, int n_active, const int32_t* active, const double
   }
   rt.n16 = 0;
   for (int q = 1; q <= kBand16MaxQ; ++q) rt.n16 += (int)b16_ids[q].size();
-  // the dense class: isotropic specs first, then the ARD ones (their own build and contraction)
+  // the dense class: isotropic specs first, then the ARD ones, then the Coregion ones (each with
+  // its own build and contraction; n_ard counts the ARD and the Coregion ones)
   const auto first_ard = std::stable_partition(order.begin(), order.end(),
-                                               [&](int32_t b) { return !ard_spec(bt->specs[b]); });
+                                               [&](int32_t b) { return dense_class(bt->specs[b]) == 0; });
   rt.n_ard = (int)(order.end() - first_ard);
+  const auto first_cg = std::stable_partition(first_ard, order.end(),
+                                              [&](int32_t b) { return dense_class(bt->specs[b]) != 2; });
+  rt.n_cg = (int)(order.end() - first_cg);
   rt.n_dense = (int)order.size();
   rt.n_band = (int)band_ids.size();
   rt.n_fused = (int)fused_ids.size() + rt.n16;
@@ -331,6 +335,30 @@ bool ard_spec(const gpx_kernel_spec& sp) {
   return false;
 }
 
+// a spec with a Coregion term (GPX_COREGION): never banded (no band kind), always the dense route's
+// Coregion kernels, whatever its partner terms are
+bool coreg_spec(const gpx_kernel_spec& sp) {
+  for (int t = 0; t < sp.n_terms && t < GPX_MAX_TERMS; ++t)
+    if (sp.terms[t].kind == GPX_COREGION) return true;
+  return false;
+}
+
+int dense_class(const gpx_kernel_spec& sp) { return coreg_spec(sp) ? 2 : ard_spec(sp) ? 1 : 0; }
+
+unsigned signed_slot_mask(const gpx_kernel_spec& sp) {
+  unsigned m = 0;
+  const int P = sp.reserved & 0xff, R = (sp.reserved >> 8) & 0xff;
+  for (int t = 0; t < sp.n_terms && t < GPX_MAX_TERMS; ++t) {
+    if (sp.terms[t].kind != GPX_COREGION) continue;
+    for (int e = 0; e < P * R; ++e) {
+      const int p = sp.terms[t].param_offset + e;
+      if (p >= 0 && p < GPX_THETA_STRIDE) m |= 1u << p;
+    }
+  }
+  return m;
+}
+
+// (a Coregion term's count depends on the spec's P and R: spec_error counts it itself)
 int term_param_count(const gpx_term& tm) {
   const int kind = tm.kind & GPX_TERM_KIND_MASK;
   const int np = (kind == GPX_RQ || kind == GPX_PERIODIC_SE) ? 3 : (kind == GPX_LINEAR ? 1 : 2);
@@ -341,13 +369,27 @@ const char* spec_error(const gpx_kernel_spec& sp, int D) {
   if (sp.n_terms < 1 || sp.n_terms > GPX_MAX_TERMS || sp.n_params < 1 || sp.n_params >= GPX_THETA_STRIDE)
     return "bad kernel spec";
   int staged = 0;
-  bool ard = false, raw = false;
+  bool ard = false, raw = false, coreg = false;
   for (int t = 0; t < sp.n_terms; ++t) {
     const gpx_term& tm = sp.terms[t];
     const int kind = tm.kind & GPX_TERM_KIND_MASK;
-    if ((tm.kind & ~(GPX_TERM_ARD | GPX_TERM_KIND_MASK)) != 0 || kind < GPX_SE || kind > GPX_LINEAR ||
+    if ((tm.kind & ~(GPX_TERM_ARD | GPX_TERM_KIND_MASK)) != 0 || kind < GPX_SE || kind > GPX_COREGION ||
         tm.dim_start < 0 || tm.dim_count < 1 || tm.dim_start + tm.dim_count > D || tm.param_offset < 0)
       return "bad kernel term";
+    if (kind == GPX_COREGION) {
+      // P | R << 8 in reserved; θ slots [W row-major (P·R), κ (P)]
+      const int P = sp.reserved & 0xff, R = (sp.reserved >> 8) & 0xff;
+      if (tm.kind & GPX_TERM_ARD) return "GPX_TERM_ARD is valid with the SE, Matern, Exponential and RationalQuadratic kinds only";
+      if (tm.dim_count != 1) return "a Coregion term acts on exactly one input column (dim_count == 1)";
+      if (coreg) return "a spec may hold one Coregion term";
+      if (P < 1 || R < 1 || (sp.reserved & ~0xffff) != 0)
+        return "a Coregion spec needs P >= 1 and R >= 1 in reserved (P | R << 8)";
+      if (sp.n_terms > 1 && sp.combine != GPX_PRODUCT)
+        return "a Coregion term is valid alone or in a GPX_PRODUCT spec, not in a GPX_SUM";
+      if (tm.param_offset + P * R + P > sp.n_params) return "bad kernel term";
+      coreg = true;
+      continue;
+    }
     if (tm.kind & GPX_TERM_ARD) {
       if (kind > GPX_RQ) return "GPX_TERM_ARD is valid with the SE, Matern, Exponential and RationalQuadratic kinds only";
       if (tm.dim_count < 2) return "GPX_TERM_ARD needs dim_count >= 2 (one active dim: the plain term)";
@@ -363,12 +405,25 @@ const char* spec_error(const gpx_kernel_spec& sp, int D) {
     return "an ARD spec may use GPX_THETA_STRIDE - 1 columns of the theta row (kernel parameters + noise)";
   if (ard && staged + (raw ? D : 0) > GPX_MAX_DIM)
     return "an ARD spec's stationary terms cover more than GPX_MAX_DIM input columns in total";
+  if (!coreg && sp.reserved != 0) return "reserved must be 0 in a spec without a Coregion term";
+  if (coreg && sp.n_params + 1 > GPX_THETA_STRIDE - 1)
+    return "a Coregion spec may use GPX_THETA_STRIDE - 1 columns of the theta row (kernel parameters + noise)";
+  // (the Coregion kernels stage the partner terms' rows as the ARD kernels do, and the rows' output
+  // indices in one more column)
+  if (coreg && staged + (raw ? D : 0) + 1 > GPX_MAX_DIM)
+    return "a Coregion spec's partner terms cover more than GPX_MAX_DIM - 1 input columns in total";
   return nullptr;
 }
 
 }  // namespace gpx
 
 extern "C" {
+
+int gpx_spec_signed_mask(const gpx_kernel_spec* spec, int D, uint32_t* mask_out) {
+  if (!spec || !mask_out || D < 1 || D > GPX_MAX_DIM || spec_error(*spec, D)) return GPX_BAD_ARG;
+  *mask_out = signed_slot_mask(*spec);
+  return GPX_OK;
+}
 
 int gpx_batch_band_width(gpx_batch* bt, int n_rows, const int32_t* rows, const double* theta, int32_t* p_out) {
   if (!bt) return GPX_BAD_ARG;
@@ -383,7 +438,7 @@ int gpx_batch_band_width(gpx_batch* bt, int n_rows, const int32_t* rows, const d
       p_out[i] = -2;
       continue;
     }
-    // (a spec with an ARD term: band_width's −1, dense)
+    // (a spec with an ARD or a Coregion term: band_width's −1, dense)
     const int p = plim >= 0 ? band_width(bt, b, theta + (size_t)b * GPX_THETA_STRIDE) : -1;
     p_out[i] = (p >= 0 && p <= plim) ? p : -1;
   }

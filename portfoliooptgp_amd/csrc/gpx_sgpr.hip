@@ -184,6 +184,7 @@ int gpx_sgpr_create(gpx_ctx* ctx, int N, int M, int D, const double* X, const do
   if (N < 1 || M < 1 || D < 1 || D > GPX_MAX_DIM || !X || !Y || !spec)
     return fail(ctx, GPX_BAD_ARG, "bad sgpr dimensions or null pointer");
   if (ard_spec(*spec)) return fail(ctx, GPX_BAD_ARG, "ARD terms (GPX_TERM_ARD) are served by the gpx_batch_* entry points only");
+  if (coreg_spec(*spec)) return fail(ctx, GPX_BAD_ARG, kCoregBatchOnlyMsg);
   HIPX(ctx, hipSetDevice(ctx->device));
   gpx_sgpr* sg = new gpx_sgpr();
   sg->ctx = ctx; sg->N = N; sg->M = M; sg->D = D; sg->X = X; sg->Y = Y; sg->spec = *spec;

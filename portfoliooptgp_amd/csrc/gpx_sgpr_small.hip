@@ -661,6 +661,7 @@ int gpx_sgpr_small_bind(gpx_sgpr_small* sm, int b, int n, int m, const double* X
   if (n > sm->Nmax || m > sm->Mmax)
     return fail(ctx, GPX_BAD_ARG, "model larger than the object's N_max / M_max");
   if (ard_spec(*spec)) return fail(ctx, GPX_BAD_ARG, kArdMsg);
+  if (coreg_spec(*spec)) return fail(ctx, GPX_BAD_ARG, kCoregBatchOnlyMsg);
   if (const char* why = spec_error(*spec, sm->D)) return fail(ctx, GPX_BAD_ARG, why);
   HIPX(ctx, hipSetDevice(ctx->device));
   SgprMeta meta;

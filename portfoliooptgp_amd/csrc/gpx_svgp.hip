@@ -297,6 +297,7 @@ int create_impl(gpx_ctx* ctx, int N, int M, int D, const double* X, const double
       n_total < N)
     return fail(ctx, GPX_BAD_ARG, "bad svgp dimensions or null pointer");
   if (ard_spec(*spec)) return fail(ctx, GPX_BAD_ARG, "ARD terms (GPX_TERM_ARD) are served by the gpx_batch_* entry points only");
+  if (coreg_spec(*spec)) return fail(ctx, GPX_BAD_ARG, kCoregBatchOnlyMsg);
   HIPX(ctx, hipSetDevice(ctx->device));
   gpx_svgp* sv = new gpx_svgp();
   sv->ctx = ctx; sv->N = N; sv->M = M; sv->D = D; sv->X = X; sv->Y = Y; sv->spec = *spec;

@@ -133,6 +133,7 @@ int gpx_vgp_create(gpx_ctx* ctx, int N, int D, const double* X, const double* Y,
   if (N < 1 || D < 1 || D > GPX_MAX_DIM || !X || !Y || !spec)
     return fail(ctx, GPX_BAD_ARG, "bad vgp dimensions or null pointer");
   if (ard_spec(*spec)) return fail(ctx, GPX_BAD_ARG, "ARD terms (GPX_TERM_ARD) are served by the gpx_batch_* entry points only");
+  if (coreg_spec(*spec)) return fail(ctx, GPX_BAD_ARG, kCoregBatchOnlyMsg);
   if (likelihood != GPX_LIK_GAUSSIAN && likelihood != GPX_LIK_STUDENT_T)
     return fail(ctx, GPX_BAD_ARG, "unknown vgp likelihood");
   if (likelihood == GPX_LIK_STUDENT_T && (!(df > 0.0) || !std::isfinite(df)))

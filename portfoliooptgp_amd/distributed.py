@@ -127,12 +127,14 @@ def fit_cost(n: int, band_blocks: Optional[int] = None, band16_q: Optional[int] 
 def series_cost(x, kernel=None) -> float:
     """fit_cost of a series for the default fitter (SE at GPflow's default ℓ = 1), on the path
     the device routes it to at that ℓ. ``kernel``: the fit's kernel when it is not the default
-    one; a kernel with ARD lengthscales over several dims always runs dense."""
+    one; a kernel with ARD lengthscales over several dims, or with a Coregion term, always runs dense."""
     if kernel is not None:
+        from . import _native as N
         from .kernels import compile_spec
         xa = np.asarray(x)
         spec = compile_spec(kernel, 1 if xa.ndim == 1 else int(xa.shape[1]))
-        if any(spec.terms[t].kind & 0x100 for t in range(spec.n_terms)):  # (GPX_TERM_ARD, include/gpx.h)
+        if any(spec.terms[t].kind & N.GPX_TERM_ARD or spec.terms[t].kind == N.GPX_COREGION
+               for t in range(spec.n_terms)):
             return fit_cost(len(x))
     return fit_cost(len(x), band_blocks_estimate(x), band16_estimate(x))
 

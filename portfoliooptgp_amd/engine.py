@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from .kernels import signed_slot_mask
 
 
 def default_device() -> int:
@@ -57,14 +58,23 @@ def _rows(x: torch.Tensor, D: int) -> torch.Tensor:
     return x.reshape(x.shape[0], -1)
 
 
-def screen_theta(act: np.ndarray, theta: np.ndarray, n_params: np.ndarray, info: np.ndarray) -> np.ndarray:
-    """Active rows whose constrained θ (kernel parameters + σn²) are all finite and > 0; the
-    others get info = INFO_BAD_THETA and stay out of the device call, so one fit whose softplus
-    underflowed does not fail its whole batch (gpx_batch_lml_grad rejects the call otherwise)."""
+_COLS = np.arange(N.GPX_THETA_STRIDE)
+
+
+def screen_theta(act: np.ndarray, theta: np.ndarray, n_params: np.ndarray, info: np.ndarray,
+                 signed: Optional[np.ndarray] = None) -> np.ndarray:
+    """Active rows whose constrained θ (kernel parameters + σn²) are all finite and > 0 (the signed
+    slots of ``signed[b]``, a Coregion W: finite); the others get info = INFO_BAD_THETA and stay out
+    of the device call, so one fit whose softplus underflowed does not fail its whole batch
+    (gpx_batch_lml_grad rejects the call otherwise)."""
     if np.isfinite(theta).all() and (theta > 0.0).all():  # the usual case, one pass
         return act
-    ok = np.array([bool(np.all(np.isfinite(theta[b, : n_params[b] + 1]) & (theta[b, : n_params[b] + 1] > 0.0)))
-                   for b in act], dtype=bool)
+    # the active rows at once: a column counts up to the row's σn²; it may be <= 0 only where the
+    # row's mask has its bit (rows of specs without a Coregion term have no bit set)
+    th = theta[act]
+    used = _COLS[None, :] <= np.asarray(n_params)[act][:, None]
+    free = np.zeros_like(used) if signed is None else ((np.asarray(signed)[act][:, None] >> _COLS[None, :]) & 1) == 1
+    ok = ((np.isfinite(th) & ((th > 0.0) | free)) | ~used).all(axis=1)
     if ok.all():
         return act
     info[act[~ok]] = N.INFO_BAD_THETA
@@ -177,6 +187,8 @@ class Engine:
         self.band_route = "sweeps"
         self.set_band_route(_DEFAULT_BAND_ROUTE if band_route is None else band_route)
         self.n_params = np.asarray([s.n_params for s in specs], dtype=np.int64)
+        # per slot, the bit mask of its signed θ columns (a Coregion term's W; 0 for every other spec)
+        self.signed = np.asarray([signed_slot_mask(s) for s in specs], dtype=np.int64)
         self.eval_count = 0
         self._rebound = {}  # slot -> device tensors of its last rebind (kept alive for the gather)
         # (id(X), id(Y)) -> what rebind derives from a device pair whose X is marked immutable
@@ -232,7 +244,7 @@ class Engine:
         lml = np.full(self.B, np.nan)
         grad = np.full((self.B, N.GPX_THETA_STRIDE), np.nan)
         info = np.full(self.B, N.INFO_UNSET if self.deferral >= 0 else 0, dtype=np.int32)
-        act = screen_theta(act, theta, self.n_params, info)
+        act = screen_theta(act, theta, self.n_params, info, self.signed)
         if len(act) == 0:
             return lml, grad, info
         dp = ctypes.POINTER(ctypes.c_double)
@@ -269,8 +281,9 @@ class Engine:
                                    grad.ctypes.data, info.ctypes.data)
         th, lml, grad, info, act, fn, pa, pt, pl, pg, pi = fp
         np_b = int(self.n_params[b])
-        for v in row[:np_b + 1].tolist():
-            if not (0.0 < v < float("inf")):
+        sg = int(self.signed[b])
+        for p, v in enumerate(row[:np_b + 1].tolist()):
+            if not (0.0 < v < float("inf")) and not ((sg >> p) & 1 and -float("inf") < v < float("inf")):
                 info[b] = N.INFO_BAD_THETA
                 return float("nan"), np.full(N.GPX_THETA_STRIDE, np.nan), N.INFO_BAD_THETA
         th[b] = row
@@ -305,7 +318,7 @@ class Engine:
         # (with deferral a complete reports on the call's rows and on earlier deferred rows it
         # delivers; every other row keeps INFO_UNSET)
         info = np.full(self.B, N.INFO_UNSET if self.deferral >= 0 else 0, dtype=np.int32)
-        act = screen_theta(act, theta, self.n_params, info)
+        act = screen_theta(act, theta, self.n_params, info, self.signed)
         self._submitted = (act, lml, grad, info)
         if len(act) == 0:
             return
@@ -559,6 +572,7 @@ class Engine:
             return self._rebind_dev(b, x, y, n, spec, ent)
         self.specs[b] = spec
         self.n_params[b] = spec.n_params
+        self.signed[b] = signed_slot_mask(spec)
         self.n[b] = n
         self._means.pop(b, None)  # (the library resets a rebound slot to zero mean)
         if box is not None:
@@ -591,6 +605,7 @@ class Engine:
             box_ptr = ent[3][1]
         self.specs[b] = spec
         self.n_params[b] = spec.n_params
+        self.signed[b] = signed_slot_mask(spec)
         self.n[b] = n
         if self._means:
             self._means.pop(b, None)

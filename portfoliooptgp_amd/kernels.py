@@ -12,6 +12,12 @@ ARD: the stationary kernels take ``lengthscales`` as a scalar or as a 1-D sequen
 per active dim (``kernel.ard`` is then True, as in GPflow). The vector is one trainable variable;
 in the θ row it is flattened where the scalar sits: ``[ℓ_0 … ℓ_{dn−1}, σ²]``, RationalQuadratic
 ``[α, ℓ_0 … ℓ_{dn−1}, σ²]``. Served by ``models.GPR`` (the dense route); see DESIGN.md §3h.
+
+Coregion: ``Coregion(output_dim=P, rank=R, active_dims=[index column])`` is gpflow.kernels.Coregion,
+the intrinsic coregionalisation model: ``K[i, j] = B[a_i, a_j]`` with ``B = W Wᵀ + diag(κ)`` and a the
+integer output index in the one active column. ``W`` ([P, R], identity transform, signed) takes P·R θ
+columns in row-major order, ``kappa`` ([P], positive) the P behind them. Alone or as one factor of a
+flat ``Product``; served by ``models.GPR`` (the dense route); see DESIGN.md §3k.
 """
 from __future__ import annotations
 
@@ -20,7 +26,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native as N
-from .parameter import Parameter, VectorParameter
+from .parameter import ArrayParameter, Parameter, VectorParameter
 
 
 def _normalise_active_dims(active_dims) -> Optional[Tuple[int, int]]:
@@ -66,11 +72,14 @@ class Kernel:
 
     def _theta_slots(self) -> List[Tuple[object, Optional[int]]]:
         """The kernel's θ columns in order: (parameter, entry) per column — entry None for a
-        scalar parameter, the index into its vector for an ARD lengthscale."""
+        scalar parameter, the index into its vector for an ARD lengthscale or a Coregion κ, the
+        row-major index into a Coregion W."""
         out: List[Tuple[object, Optional[int]]] = []
         for p in self.parameters:
             if isinstance(p, VectorParameter):
                 out.extend((p, e) for e in range(p.size))
+            elif isinstance(p, ArrayParameter):
+                out.extend((p, e) for e in range(int(np.prod(p.shape))))
             else:
                 out.append((p, None))
         return out
@@ -79,8 +88,8 @@ class Kernel:
         """Constrained values of the θ columns (``_theta_slots`` order)."""
         out: List[float] = []
         for p in self.parameters:
-            if isinstance(p, VectorParameter):
-                out.extend(p.value.tolist())
+            if isinstance(p, (VectorParameter, ArrayParameter)):
+                out.extend(p.value.reshape(-1).tolist())
             else:
                 out.append(p.value)
         return out
@@ -100,8 +109,8 @@ class Kernel:
 
     def __repr__(self) -> str:
         def show(p):
-            if isinstance(p, VectorParameter):
-                return "[" + ", ".join(f"{v:.6g}" for v in p.value.tolist()) + "]"
+            if isinstance(p, (VectorParameter, ArrayParameter)):
+                return "[" + ", ".join(f"{v:.6g}" for v in p.value.reshape(-1).tolist()) + "]"
             return f"{p.value:.6g}"
         return f"<{type(self).__name__} " + ", ".join(
             f"{n}={show(p)}" for n, p in self._param_paths("")) + ">"
@@ -252,6 +261,60 @@ class Periodic(_Term):
         return self.base_kernel._param_paths(prefix + "base_kernel.") + [(prefix + "period", self.period)]
 
 
+class Coregion(_Term):
+    """gpflow.kernels.Coregion(output_dim, rank, active_dims=[index column]): K[i, j] = B[a_i, a_j],
+    B = W Wᵀ + diag(κ), a the integer output index held by the one active column. Params ordered
+    [W, kappa] (tf.Module: attribute names in ASCII order); W [P, R] has the identity transform
+    (default 0.1·ones, any sign), kappa [P] is positive (default ones)."""
+    kind = N.GPX_COREGION
+
+    def __init__(self, output_dim: int, rank: int, *, active_dims=None, name=None):
+        super().__init__(active_dims=active_dims, name=name)
+        P, R = int(output_dim), int(rank)
+        if P < 1 or R < 1:
+            raise ValueError(f"{self.name}: output_dim and rank must be >= 1")
+        if self._dims is not None and self._dims[1] != 1:
+            raise ValueError(f"{self.name}: Coregion acts on exactly one input column (the output index); "
+                             f"active_dims {active_dims} selects {self._dims[1] if self._dims[1] >= 0 else 'several'}")
+        self.output_dim, self.rank = P, R
+        self.W = ArrayParameter(0.1 * np.ones((P, R)), name="W")
+        self.W.summary_full = True  # (print_summary shows the whole matrix: at most 14 entries)
+        self.kappa = VectorParameter(np.ones(P), name="kappa")
+
+    def output_covariance(self) -> np.ndarray:
+        """B = W Wᵀ + diag(κ), [P, P]."""
+        W = self.W.value
+        return W @ W.T + np.diag(self.kappa.value)
+
+    def output_variance(self) -> np.ndarray:
+        """diag(B) = Σ_r W_pr² + κ_p, [P]."""
+        return np.sum(np.square(self.W.value), axis=1) + self.kappa.value
+
+    def _spec_term(self, D: int, offset: int) -> N.GpxTerm:
+        start, count = self._active(D)
+        if count != 1:
+            raise ValueError(f"{self.name}: Coregion acts on exactly one input column (the output index); "
+                             f"active_dims {self.active_dims} selects {count} of D={D}")
+        return N.GpxTerm(self.kind, start, 1, offset)
+
+    def check_index(self, X, what: str = "X") -> None:
+        """Every value of the index column must be an exact integer in [0, output_dim)."""
+        X = np.asarray(X, dtype=np.float64)
+        start, _ = self._active(X.shape[1])
+        col = X[:, start]
+        if not (np.all(np.isfinite(col)) and np.all(col == np.floor(col)) and np.all(col >= 0)
+                and np.all(col < self.output_dim)):
+            raise ValueError(f"{self.name}: column {start} of {what} must hold integer output indices in "
+                             f"[0, {self.output_dim})")
+
+    @property
+    def parameters(self):
+        return (self.W, self.kappa)
+
+    def _param_paths(self, prefix):
+        return [(prefix + "W", self.W), (prefix + "kappa", self.kappa)]
+
+
 class Combination(Kernel):
     """Sum / Product; nested combinations of the same class are flattened like GPflow's
     Combination._set_kernels."""
@@ -310,11 +373,20 @@ def compile_spec(kernel: Kernel, D: int) -> N.GpxKernelSpec:
     spec = N.GpxKernelSpec()
     spec.n_terms = len(terms)
     spec.combine = kernel._combine()
+    coreg = [k for k in terms if isinstance(k, Coregion)]
+    if coreg:
+        # one Coregion term, alone or as a factor of a flat product (include/gpx.h)
+        if len(coreg) > 1:
+            raise NotImplementedError("a kernel may hold one Coregion term (two Coregion factors are not provided)")
+        if len(terms) > 1 and kernel._combine() != N.GPX_PRODUCT:
+            raise NotImplementedError("Coregion inside a Sum is not provided: use it alone or as one factor of "
+                                      "a flat Product (k_t * Coregion)")
+        spec.reserved = coreg[0].output_dim | (coreg[0].rank << 8)
     off = 0
     for t, term in enumerate(terms):
         spec.terms[t] = term._spec_term(D, off)
         off += len(term._theta_slots())
-    if off + 1 > N.GPX_THETA_STRIDE:
+    if off + 1 > N.GPX_THETA_STRIDE and not coreg:  # (a Coregion kernel: its own row rule below)
         raise NotImplementedError(
             f"too many kernel parameters: the θ row holds {N.GPX_THETA_STRIDE} values, this kernel needs "
             f"{off} + the noise variance")
@@ -330,8 +402,54 @@ def compile_spec(kernel: Kernel, D: int) -> N.GpxKernelSpec:
         if staged + (D if any(not isinstance(k, Stationary) for k in terms) else 0) > N.GPX_MAX_DIM:
             raise NotImplementedError(
                 f"an ARD kernel's stationary terms may cover at most {N.GPX_MAX_DIM} input columns in total")
+    if coreg:
+        # the same row rule as an ARD spec; the Coregion kernels stage the partners' rows as the ARD
+        # kernels do, plus the rows' output indices in one more column
+        if off + 1 > N.GPX_THETA_STRIDE - 1:
+            raise NotImplementedError(
+                f"too many kernel parameters for a Coregion kernel: the θ row holds GPX_THETA_STRIDE = "
+                f"{N.GPX_THETA_STRIDE} values, of which a Coregion kernel and the noise variance may use "
+                f"{N.GPX_THETA_STRIDE - 1}; this one needs {off + 1} (P·R + P for W and kappa)")
+        partners = [(t, k) for t, k in enumerate(terms) if not isinstance(k, Coregion)]
+        staged = sum(spec.terms[t].dim_count for t, k in partners if isinstance(k, Stationary))
+        if staged + (D if any(not isinstance(k, Stationary) for _, k in partners) else 0) + 1 > N.GPX_MAX_DIM:
+            raise NotImplementedError(
+                f"a Coregion kernel's partner terms may cover at most {N.GPX_MAX_DIM - 1} input columns in total")
     spec.n_params = off
     return spec
+
+
+def has_coregion(kernel: Kernel) -> bool:
+    """True when some term of ``kernel`` is a Coregion term."""
+    def walk(k):
+        if isinstance(k, Combination):
+            return any(walk(c) for c in k.kernels)
+        return isinstance(k, Coregion)
+    return walk(kernel)
+
+
+def coregion_term(kernel: Kernel) -> Optional["Coregion"]:
+    """The Coregion term of a flat kernel, or None."""
+    for k in kernel._terms():
+        if isinstance(k, Coregion):
+            return k
+    return None
+
+
+def signed_slot_mask(spec: N.GpxKernelSpec) -> int:
+    """Bit p set: θ column p of ``spec`` is signed — a Coregion term's W entries, which may be any
+    finite value. Every other kernel parameter (κ included) and the noise variance must be finite
+    and > 0. The twin of signed_slot_mask in csrc/gpx_route.hip (gpx_spec_signed_mask)."""
+    m = 0
+    P, R = spec.reserved & 0xFF, (spec.reserved >> 8) & 0xFF
+    for t in range(min(spec.n_terms, N.GPX_MAX_TERMS)):
+        if spec.terms[t].kind != N.GPX_COREGION:
+            continue
+        for e in range(P * R):
+            p = spec.terms[t].param_offset + e
+            if 0 <= p < N.GPX_THETA_STRIDE:
+                m |= 1 << p
+    return m
 
 
 def has_ard(kernel: Kernel) -> bool:

@@ -21,7 +21,7 @@ import torch
 
 from . import _native as N
 from .engine import Engine, default_device, solo_engine
-from .kernels import Kernel, compile_spec, has_ard
+from .kernels import Kernel, compile_spec, coregion_term, has_ard, has_coregion
 from .likelihoods import Gaussian, StudentT
 from .mean_functions import MeanFunction, Zero
 from .parameter import ArrayParameter, Parameter, VectorParameter, sigmoid
@@ -33,6 +33,14 @@ def _refuse_ard(kernel: Kernel, model: str) -> None:
     if has_ard(kernel):
         raise NotImplementedError(f"{model} takes kernels with scalar lengthscales: ARD (vector) "
                                   "lengthscales are implemented for models.GPR")
+
+
+def _refuse_coregion(kernel: Kernel, model: str) -> None:
+    """Coregion kernels are served by models.GPR (the dense route's Coregion kernels); the sparse /
+    variational models evaluate K through the isotropic device functions."""
+    if has_coregion(kernel):
+        raise NotImplementedError(f"{model} does not take kernels with a Coregion term: Coregion is "
+                                  "implemented for models.GPR")
 
 
 class GPR:
@@ -75,6 +83,10 @@ class GPR:
         self.num_latent_gps = 1
         self.device = default_device() if device is None else int(device)
         self._spec = compile_spec(kernel, Xt.shape[1])
+        # a Coregion term: the index column of X must hold exact integers in [0, P)
+        self._coreg = coregion_term(kernel)
+        if self._coreg is not None:
+            self._coreg.check_index(Xt.detach().cpu().numpy(), "X")
         self._mean = mean_function if mean_function is not None and mean_function.n_coef > 0 else None
         if self._mean is not None:
             self._mean._check_dim(int(Xt.shape[1]))
@@ -149,7 +161,8 @@ class GPR:
         row = self.theta_row()
         lml, grad, info = eng.lml_grad_row(b, row)
         if info == N.INFO_BAD_THETA:
-            raise N.InvalidParameterError(f"hyperparameters out of (0, inf): {row[:eng.n_params[b] + 1]}")
+            raise N.InvalidParameterError("hyperparameters out of range (every kernel parameter and the noise "
+                                          f"finite and > 0, a Coregion W finite): {row[:eng.n_params[b] + 1]}")
         if info != 0:
             raise N.NotPositiveDefiniteError(
                 f"Cholesky decomposition was not successful: pivot {int(info)} of K + noise I "
@@ -183,7 +196,9 @@ class GPR:
         if cache is None or cache[0] is not variables:
             pindex, nk = {}, 0  # parameter -> (first column, columns)
             for p in self.kernel.parameters:
-                cnt = p.size if isinstance(p, VectorParameter) else 1
+                # (a Coregion W: one column per entry, row-major, the identity transform)
+                cnt = (p.size if isinstance(p, VectorParameter)
+                       else int(np.prod(p.shape)) if isinstance(p, ArrayParameter) else 1)
                 pindex[id(p)] = (nk, cnt)
                 nk += cnt
             mindex, o = {}, nk + 1
@@ -201,7 +216,7 @@ class GPR:
                     c0, cnt = pindex[id(p)]
                     rows.extend(range(c0, c0 + cnt))
                     params.extend([p] * cnt)
-                    ents.extend(range(cnt) if isinstance(p, VectorParameter) else [None])
+                    ents.extend(range(cnt) if isinstance(p, VectorParameter) else [None] * cnt)
                 elif id(p) in mindex:
                     c0, cnt = mindex[id(p)]
                     rows.extend(range(c0, c0 + cnt))
@@ -257,6 +272,9 @@ class GPR:
         return self._predict(Xnew, add_noise=True)
 
     def _predict(self, Xnew, add_noise: bool, full_cov: bool = False):
+        if self._coreg is not None:  # (a Coregion term: Xnew's index column is checked like X's)
+            xn = Xnew.detach().cpu().numpy() if isinstance(Xnew, torch.Tensor) else np.asarray(Xnew, dtype=np.float64)
+            self._coreg.check_index(xn.reshape(xn.shape[0], -1) if xn.ndim != 2 else xn, "Xnew")
         eng, b = self.engine()
         theta = np.ones((eng.B, N.GPX_THETA_STRIDE))
         theta[b] = self.theta_row()
@@ -335,6 +353,7 @@ class SVGP:
             raise NotImplementedError("SVGP evaluates the StudentT likelihood by the per-point route only: pass "
                                       "per_point=True (the Gaussian and StudentT likelihoods are supported)")
         _refuse_ard(kernel, "SVGP")
+        _refuse_coregion(kernel, "SVGP")
         self.kernel = kernel
         self.likelihood = likelihood
         self.inducing_variable = (inducing_variable if isinstance(inducing_variable, InducingPoints)
@@ -551,6 +570,7 @@ class SGPR:
             raise NotImplementedError("SGPR supports the Gaussian likelihood")
         self.data = (Xt, Yt)
         _refuse_ard(kernel, "SGPR")
+        _refuse_coregion(kernel, "SGPR")
         self.kernel = kernel
         self.likelihood = likelihood
         self.mean_function = mean_function
@@ -725,6 +745,7 @@ class VGP:
         n = int(Xt.shape[0])
         self.data = (Xt, Yt)
         _refuse_ard(kernel, "VGP")
+        _refuse_coregion(kernel, "VGP")
         self.kernel = kernel
         self.likelihood = likelihood
         self.mean_function = mean_function

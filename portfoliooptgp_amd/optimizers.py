@@ -75,6 +75,7 @@ class ModelStream(Sequence):
         if m is None:
             m = self._factory(i)
             _refuse_streamed_mean(m, i)  # (before the model reaches a device slot)
+            _refuse_coregion(getattr(m, "kernel", None), f"minimize_stream (model {i})")
             self._built[i] = m
         return m
 
@@ -117,6 +118,15 @@ def _refuse_streamed_mean(model, i) -> None:
         raise NotImplementedError(
             f"minimize_stream does not support mean functions (model {i}: GPR with "
             f"{type(model.mean_function).__name__}); fit it with Scipy().minimize or minimize_batch")
+
+
+def _refuse_coregion(kernel, where: str) -> None:
+    """Coregion kernels are served by models.GPR through Scipy().minimize and minimize_batch (the
+    dense route); the streamed driver's band storage and the sparse / variational batches are not."""
+    from .kernels import Kernel, has_coregion
+    if isinstance(kernel, Kernel) and has_coregion(kernel):
+        raise NotImplementedError(f"{where} does not support Coregion kernels: fit a models.GPR with "
+                                  "Scipy().minimize or minimize_batch")
 
 
 def _not_pd_policy(on_not_pd: str):
@@ -371,6 +381,7 @@ class Scipy:
         for i, m in enumerate(models):
             if not isinstance(m, SVGP):
                 raise TypeError(f"model {i} is not a models.SVGP")
+            _refuse_coregion(m.kernel, f"minimize_svgp_batch (model {i})")
             if isinstance(m.likelihood, StudentT):
                 raise NotImplementedError(f"minimize_svgp_batch: model {i} has the StudentT likelihood, which is "
                                           "evaluated by the per-point route; fit it with Scipy().minimize")
@@ -487,6 +498,7 @@ class Scipy:
         for i, m in enumerate(models):
             if not isinstance(m, SGPR):
                 raise TypeError(f"model {i} is not a models.SGPR")
+            _refuse_coregion(m.kernel, f"minimize_sgpr_batch (model {i})")
         shapes = [(int(m.data[0].shape[0]), int(m.data[0].shape[1])) for m in models]
         dims = sorted({d for _, d in shapes})
         if len(dims) != 1:
@@ -595,6 +607,7 @@ class Scipy:
             models = list(models)
             for i, m in enumerate(models):  # (a ModelStream's models are checked as they are built)
                 _refuse_streamed_mean(m, i)
+                _refuse_coregion(getattr(m, "kernel", None), f"minimize_stream (model {i})")
         if len(models) == 0:
             return [], ([] if predict_train else None)
         width = max(1, min(int(width), len(models)))
@@ -1146,10 +1159,10 @@ class _SteppedDriver:
         if not variables:
             raise ValueError("model has no trainable variables")
         cols, lower = m.theta_layout(variables)
-        # a layout with an identity variable (a mean-function coefficient) carries its transform
-        # codes and takes the _t host helpers; every other layout keeps the softplus-only ones
+        # a layout with an identity variable (a mean-function coefficient, a Coregion W) carries its
+        # transform codes and takes the _t host helpers; every other layout keeps the softplus-only ones
         tcode = None
-        if getattr(m, "mean_function", None) is not None:
+        if getattr(m, "mean_function", None) is not None or getattr(m, "_coreg", None) is not None:
             tc = m.theta_layout(variables, transforms=True)[2]
             if tc.any():
                 tcode = tc

@@ -42,6 +42,53 @@ def mean_squared_error(y_true, y_pred) -> float:
     return float(np.average((a - b) ** 2, axis=0).mean())
 
 
+def stack_assets(series):
+    """Stack several assets' series into one data set for a Coregion kernel (GPflow's intrinsic
+    coregionalisation layout): ``series`` is ``[(X_p [n_p, D], Y_p [n_p, 1])]``, one pair per asset,
+    the counts n_p may differ. Returns ``(X_aug [Σn_p, D+1], Y_aug [Σn_p, 1], index_dim)``: the rows
+    asset by asset, the asset's index p appended as column ``index_dim = D``::
+
+        X, Y, idx = stack_assets(series)
+        k = kernels.Exponential(active_dims=slice(0, idx)) * kernels.Coregion(len(series), 1, active_dims=[idx])
+    """
+    series = list(series)
+    if not series:
+        raise ValueError("stack_assets needs at least one (X, Y) pair")
+    xs, ys, D = [], [], None
+    for p, (X, Y) in enumerate(series):
+        x = np.asarray(_np(X), dtype=np.float64)
+        y = np.asarray(_np(Y), dtype=np.float64)
+        x = x.reshape(-1, 1) if x.ndim == 1 else x
+        y = y.reshape(-1, 1)
+        if x.ndim != 2:
+            raise ValueError(f"asset {p}: X must be [n, D], got shape {x.shape}")
+        if x.shape[0] != y.shape[0]:
+            raise ValueError(f"asset {p}: X has {x.shape[0]} rows, Y {y.shape[0]}")
+        D = x.shape[1] if D is None else D
+        if x.shape[1] != D:
+            raise ValueError(f"asset {p}: X has {x.shape[1]} columns, asset 0 has {D}")
+        xs.append(np.concatenate([x, np.full((x.shape[0], 1), float(p))], axis=1))
+        ys.append(y)
+    X_aug = np.concatenate(xs, axis=0)
+    return X_aug, np.concatenate(ys, axis=0), X_aug.shape[1] - 1
+
+
+def unstack_assets(values, X_aug, index_dim: int, n_assets: Optional[int] = None):
+    """The inverse of stack_assets for anything with one row per stacked row (a prediction's mean or
+    variance, [Σn_p, ...]): the list of per-asset arrays, rows in their stacked order. Works for any
+    row order of ``X_aug`` (it selects by the index column); for stack_assets' own asset-by-asset
+    order with every asset present the results are views of ``values``."""
+    v = _np(values)
+    idx = np.asarray(_np(X_aug), dtype=np.float64)[:, index_dim].astype(np.int64)
+    if v.shape[0] != idx.shape[0]:
+        raise ValueError(f"values has {v.shape[0]} rows, X_aug {idx.shape[0]}")
+    P = int(idx.max()) + 1 if n_assets is None else int(n_assets)
+    if np.all(np.diff(idx) >= 0):  # sorted by asset: contiguous slices (views)
+        bounds = np.searchsorted(idx, np.arange(P + 1))
+        return [v[bounds[p]:bounds[p + 1]] for p in range(P)]
+    return [v[idx == p] for p in range(P)]
+
+
 class ModelTrainer:
     def __init__(self, kernel_combinations: Sequence, device: Optional[int] = None):
         self.kernel_combinations = list(kernel_combinations)

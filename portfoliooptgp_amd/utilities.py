@@ -24,7 +24,12 @@ def summary_rows(model):
     paths = model._param_paths() if hasattr(model, "_param_paths") else [
         (n, p) for n, p in model._param_paths("")]
     for name, p in paths:
-        if isinstance(p, ArrayParameter):
+        if isinstance(p, ArrayParameter) and getattr(p, "summary_full", False):
+            # (a Coregion W: the whole [P, R] matrix on one line, rows in brackets)
+            v = p.value
+            rows.append((name, "Parameter", p.transform_name, p.trainable, str(tuple(v.shape)), "float64",
+                         np.array2string(v, precision=5).replace("\n", "")))
+        elif isinstance(p, ArrayParameter):
             v = p.value
             rows.append((name, "Parameter", p.transform_name, p.trainable, str(tuple(v.shape)), "float64",
                          np.array2string(v.ravel()[:3], precision=4) + ("..." if v.size > 3 else "")))
