@@ -25,7 +25,7 @@ $(CSRC)/gpx_host_math.o: $(CSRC)/gpx_host_math.c include/gpx.h
 	gcc -O2 -fno-builtin -fno-fast-math -fPIC -std=c11 -Wall -c $< -o $@
 
 # the library's objects (the phases library below swaps in its three instrumented ones)
-OBJS := $(addprefix $(CSRC)/,gpx_kernels.o gpx_api.o gpx_knobs.o gpx_dense.o gpx_route.o gpx_eval.o gpx_predict.o gpx_ard.o gpx_coregion.o \
+OBJS := $(addprefix $(CSRC)/,gpx_kernels.o gpx_api.o gpx_knobs.o gpx_dense.o gpx_route.o gpx_eval.o gpx_predict.o gpx_sample.o gpx_ard.o gpx_coregion.o \
   gpx_band.o gpx_band16.o gpx_bcr.o gpx_mean.o gpx_svgp_kernels.o gpx_svgp_lik_kernels.o gpx_svgp.o gpx_svgp_small.o gpx_sgpr.o gpx_sgpr_small.o gpx_vgp_kernels.o gpx_vgp.o gpx_host_math.o)
 $(OBJS): $(CSRC)/gpx_knobs.h
 

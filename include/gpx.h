@@ -359,6 +359,40 @@ int gpx_batch_predict_full_cov(gpx_batch* batch, int n_active, const int32_t* ac
                                const double* theta, const double* Xnew, int M, double* mean,
                                double* cov, int32_t* info, void* stream);
 
+/*
+ * Joint draws from Gaussians on the device (GPflow's sample_mvn(full_cov=True) arithmetic), fp64:
+ * for problem b with M points and S samples
+ *   A = cov[b] + jitter*I   (one add per diagonal entry; only the lower triangle of cov is read)
+ *   L = chol(A), lower
+ *   out[b, s, i] = mean[b, i] + sum_{k <= i} L[i, k] * white[b, s, k]
+ * One algorithm for every M (right-looking, blocks of 64: diagonal block and panel per step in one
+ * kernel, trailing update and L*white^T on the batched fp64 MFMA GEMM). A problem's output bits are
+ * the same alone and inside any batch, and sample s does not depend on S.
+ * gpx_sample_mvn: every buffer is the caller's (device, fp64, contiguous): mean [B, M], cov
+ * [B, M, M], white [B, S, M] (standard normal draws, or any vectors), out [B, S, M]. info (host,
+ * [B]) gets the 1-based index of the first pivot of A that is not > 0 and finite (as LAPACK potrf),
+ * else 0; with some info[b] != 0 the call returns GPX_NOT_PD, that problem's out rows are NOT
+ * written and the other problems' are correct. The call returns when out is filled; calls on one
+ * context take turns (they share its workspace). Limits: 1 <= M <= the value of gpx_sample_limits
+ * (8192; needs no device), S >= 1, jitter finite and >= 0.
+ * gpx_batch_predict_samples: the posterior of gpx_batch_predict_full_cov at Xnew (device
+ * [B, M, D]) followed by the sampler, in one call with one synchronise: the covariance stays in the
+ * batch's workspace (no [M, M] copy-out, no host round trip). mean (device [B, M]) and out (device
+ * [B, S, M]) are written for the active rows; white is device [B, S, M], indexed by slot like them.
+ * Works on every batch gpx_batch_predict_full_cov works on (band storage, ARD, Coregion and mean
+ * function specs included). info[b] != 0 if either factorisation failed (GPX_NOT_PD);
+ * gpx_last_error names which: "K + noise*I ..." or "the posterior covariance + jitter*I ...".
+ * GPX_BAD_ARG (with a message): null pointers, M <= 0, S <= 0, M over the limit, a negative or
+ * non-finite jitter, a problem with a deferred evaluation in flight. A NULL ctx / batch is
+ * GPX_BAD_ARG without touching a device.
+ */
+int gpx_sample_limits(int* m_max);
+int gpx_sample_mvn(gpx_ctx* ctx, int B, int M, int S, const double* mean, const double* cov,
+                   const double* white, double jitter, double* out, int32_t* info, void* stream);
+int gpx_batch_predict_samples(gpx_batch* batch, int n_active, const int32_t* active, const double* theta,
+                              const double* Xnew, int M, int S, const double* white, double jitter,
+                              double* mean, double* out, int32_t* info, void* stream);
+
 /* Timing hooks for bench.py: total device time (ms) of the last call's kernels, measured with
  * HIP events on the stream they ran on, split by phase. */
 typedef struct {

@@ -57,6 +57,7 @@ EXPORTED_SYMBOLS = (
     "gpx_host_theta_rows", "gpx_host_loss_grad_u",
     "gpx_batch_set_mean", "gpx_host_theta_rows_t", "gpx_host_loss_grad_u_t",
     "gpx_spec_signed_mask",
+    "gpx_sample_limits", "gpx_sample_mvn", "gpx_batch_predict_samples",
 )
 
 
@@ -175,8 +176,16 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.gpx_batch_predict_full_cov.restype = c_int
         lib.gpx_batch_predict_full_cov.argtypes = [c_void_p, c_int, c_int_p, c_double_p, c_void_p,
                                                    c_int, c_void_p, c_void_p, c_int_p, c_void_p]
+        lib.gpx_sample_limits.restype = c_int
+        lib.gpx_sample_limits.argtypes = [ctypes.POINTER(c_int)]
+        lib.gpx_sample_mvn.restype = c_int
+        lib.gpx_sample_mvn.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_double,
+                                       c_void_p, c_int_p, c_void_p]
+        lib.gpx_batch_predict_samples.restype = c_int
+        lib.gpx_batch_predict_samples.argtypes = [c_void_p, c_int, c_int_p, c_double_p, c_void_p, c_int, c_int,
+                                                  c_void_p, c_double, c_void_p, c_void_p, c_int_p, c_void_p]
         lib.gpx_batch_predict_train.restype = c_int
-        lib.gpx_batch_predict_train.argtypes = [c_void_p, c_int, c_int_p, c_double_p, c_int, c_void_p,
+        lib.gpx_batch_predict_train.argtypes =[c_void_p, c_int, c_int_p, c_double_p, c_int, c_void_p,
                                                 c_void_p, c_int_p, c_void_p]
         lib.gpx_batch_predict_train_rows.restype = c_int
         lib.gpx_batch_predict_train_rows.argtypes = [c_void_p, c_int, c_int_p, c_double_p, c_int, c_void_p,

@@ -133,6 +133,8 @@ int gpx_destroy(gpx_ctx* ctx) {
   if (!ctx) return GPX_BAD_ARG;
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
+  if (ctx->sample.ws) (void)hipFree(ctx->sample.ws);
+  if (ctx->sample.idx) (void)hipFree(ctx->sample.idx);
   delete ctx;
   return GPX_OK;
 }
@@ -322,7 +324,7 @@ int gpx_batch_destroy(gpx_batch* bt) {
   for (void* p : {(void*)bt->K, (void*)bt->L, (void*)bt->W, (void*)bt->z, (void*)bt->alpha,
                   (void*)bt->ldiag, (void*)bt->partial, (void*)bt->d_io, (void*)bt->d_n, (void*)bt->d_orow,
                   (void*)bt->d_specs, (void*)bt->kxs, (void*)bt->pvp, (void*)bt->abuf, (void*)bt->covw,
-                  (void*)bt->bres, (void*)bt->bcr_ws, (void*)bt->bcr_ws_slow})
+                  (void*)bt->samp, (void*)bt->d_sinfo, (void*)bt->bres, (void*)bt->bcr_ws, (void*)bt->bcr_ws_slow})
     if (p) (void)hipFree(p);
   for (hipEvent_t e : bt->bcr_ev)
     if (e) (void)hipEventDestroy(e);

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 #include "gpx_internal.h"
@@ -18,10 +19,19 @@ constexpr int kEvents = 64;
 // NULL stream). Every piece of per-evaluation state (worker / aux streams, fork and join
 // events, workspace) lives in the batch, so threads that evaluate different batches of one
 // context never share mutable state; error messages are per calling thread (gpx::fail).
+// gpx_sample_mvn's workspace on a context (its buffers are the caller's, so it has no batch):
+// grow-only, one call at a time per context (mu), freed by gpx_destroy
+struct gpx_sample_ws {
+  std::mutex mu;
+  double* ws = nullptr; size_t cap = 0;  // per problem: A [Mp][Mp], padded white and product [Sp][Mp]
+  int* idx = nullptr; size_t icap = 0;   // [active: B | info: B]
+};
+
 struct gpx_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   int profiling = 0;
+  gpx_sample_ws sample;
 };
 
 struct gpx_batch {
@@ -69,6 +79,9 @@ struct gpx_batch {
   double* pvp = nullptr; size_t pvp_cap = 0;
   double* abuf = nullptr; size_t abuf_cap = 0;   // A = W·Kxs (full_cov, Mp > Np)
   double* covw = nullptr; size_t covw_cap = 0;   // padded [B][Mp][Mp] covariance
+  // gpx_batch_predict_samples: padded white and product, [B][2][Sp][Mp]; the sampler's info [B]
+  double* samp = nullptr; size_t samp_cap = 0;
+  int* d_sinfo = nullptr;
   // factor cache: theta row of the last factorisation per problem
   std::vector<double> fac_theta;
   std::vector<char> fac_valid;

@@ -309,6 +309,29 @@ int gemm_tile(const GemmArgs& a, int n_active);  // tile edge the launcher will 
 // without faulting, so the API rejects larger shapes (GPX_BAD_ARG) and the launcher asserts.
 constexpr long long kGemmMaxLd = (0x7fffffffLL - 1024) / (127LL * 8);
 
+// ---- multivariate-normal sampler (gpx_sample.hip) ---------------------------------------------
+// out[b][s][i] = mean[b][i] + Σ_{k<=i} L[i][k] white[b][s][k], L = chol(cov[b] + jitter·I), for the
+// slots b = active[0 .. na). Every buffer is indexed by slot. A is the [Mp][Mp] workspace the factor
+// is formed in (Mp = M rounded up to 64; it may be cov itself when ldc == Mp: the load is elementwise),
+// Wp / P the zero-padded white and the product, [Sp][Mp] each (Sp = S rounded up to 64).
+struct SampleArgs {
+  const int* active;
+  const double* cov; long long sCov; int ldc;     // [M][ldc], the lower triangle is read
+  const double* white; long long sWhite;          // [S][M]
+  const double* mean; long long sMean;            // [M]
+  double* out; long long sOut;                    // [S][M]; not written where info[b] != 0
+  double* A; long long sA;                        // [Mp][Mp]: A = cov + jitter·I, then L (zeros above)
+  double* Wp; double* P; long long sW;            // [Sp][Mp]
+  int* info;                                      // [slots]: first pivot that is not > 0 and finite (1-based), 0 = ok
+  int M, S, Mp, Sp;
+  double jitter;
+};
+constexpr int kSampleMaxM = 8192;  // points per problem of one sampler call (gpx_sample_limits)
+// the launch chain of one call (load, per 64-block step: diagonal + panel, trailing GEMM; product
+// GEMM; output), all on s; info[active[..]] is zeroed first
+void launch_sample_chain(const SampleArgs& a, int na, hipStream_t s);
+void launch_sample_iota(int* idx, int n, hipStream_t s);  // idx[i] = i
+
 // ---- SVGP (gpx_svgp_kernels.hip) -----------------------------------------------------
 // Row-organised derivative contraction over an M×N (or M×M) index set:
 //   Kbar_ij = u_i g_j (optional) + Y_ij (or ½(Y_ij + Y_ji) when sym)

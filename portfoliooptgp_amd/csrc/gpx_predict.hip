@@ -14,16 +14,26 @@
 
 using namespace gpx;
 
+// gpx_batch_predict_samples' part of a predict call: the covariance stays in the batch's workspace
+// and the sampler (gpx_sample.hip) runs on it behind the prediction, on the same stream, before the
+// call's one synchronise. white / out are indexed by slot like mean. failed: bit 0 some K + σn²I,
+// bit 1 some posterior covariance + jitter·I (which one gpx_last_error names)
+struct SampleTail {
+  int S; const double* white; double jitter; double* out;
+  int failed;
+};
+
 extern "C" {
 
-// Shared body of gpx_batch_predict (var != nullptr) and gpx_batch_predict_full_cov
-// (cov != nullptr).
+// Shared body of gpx_batch_predict (var != nullptr), gpx_batch_predict_full_cov (cov != nullptr)
+// and gpx_batch_predict_samples (st != nullptr).
 static int predict_impl(gpx_batch* bt, int n_active, const int32_t* active, const double* theta,
                         const double* Xnew, int M, int add_noise, double* mean, double* var,
-                        double* cov, int32_t* info, void* stream, bool train = false, bool rows = false) {
+                        double* cov, int32_t* info, void* stream, bool train = false, bool rows = false,
+                        SampleTail* st = nullptr) {
   if (!bt) return GPX_BAD_ARG;
   gpx_ctx* ctx = bt->ctx;
-  if ((!train && (!Xnew || M <= 0)) || !mean || !(var || cov) || !info)
+  if ((!train && (!Xnew || M <= 0)) || !mean || !(var || cov || st) || !info)
     return fail(ctx, GPX_BAD_ARG, "bad predict args");
   if (!train && ((long long)M + 63) / 64 * 64 > kGemmMaxLd)
     return fail(ctx, GPX_BAD_ARG, "too many prediction points for one call (kGemmMaxLd): split Xnew");
@@ -84,7 +94,13 @@ static int predict_impl(gpx_batch* bt, int n_active, const int32_t* active, cons
       if (train)
         rc = predict_impl(sh, 1, &act0, th.data(), nullptr, 0, add_noise, mean + out_row(b) * bt->Nmax,
                           var + out_row(b) * bt->Nmax, nullptr, inf.data(), s, true);
-      else
+      else if (st) {
+        // (the shadow's slot 0 stands for problem b: its white / out rows by offset)
+        SampleTail sb{st->S, st->white + (size_t)b * st->S * M, st->jitter, st->out + (size_t)b * st->S * M, 0};
+        rc = predict_impl(sh, 1, &act0, th.data(), Xnew + (size_t)b * M * bt->D, M, add_noise,
+                          mean + (size_t)b * M, nullptr, nullptr, inf.data(), s, false, false, &sb);
+        st->failed |= sb.failed;
+      } else
         rc = predict_impl(sh, 1, &act0, th.data(), Xnew + (size_t)b * M * bt->D, M, add_noise,
                           mean + (size_t)b * M, var ? var + (size_t)b * M : nullptr,
                           cov ? cov + (size_t)b * M * M : nullptr, inf.data(), s);
@@ -217,7 +233,7 @@ static int predict_impl(gpx_batch* bt, int n_active, const int32_t* active, cons
   launch_trmv_t(t, n_active, s);
   // + m(X*) (the variances below are the zero-mean model's on the residual data)
   if (bt->n_mean > 0) mean_add(bt, bt->d_active, n_active, Xnew, M, mean, s);
-  if (cov) {
+  if (cov || st) {
     // A = W · Kxs stored; cov = K(X*,X*) − AᵀA (padded rows/cols of A are exactly zero)
     double* abuf;
     if ((size_t)Mp <= (size_t)Np) {
@@ -243,11 +259,31 @@ static int predict_impl(gpx_batch* bt, int n_active, const int32_t* active, cons
     GemmArgs gc = gemm_args(abuf, Mp, abuf, Mp, bt->covw, Mp, 0, Mp, Mp, Np, 0, 0, -1.0, 1.0);
     gc.sA = skx; gc.sB = skx; gc.sC = scv;
     gemm(rr, gc, EPI_STORE, true, false);
-    for (int i = 0; i < n_active; ++i) {
+    for (int i = 0; cov && i < n_active; ++i) {
       const int b = active[i];
       HIPX(ctx, hipMemcpy2DAsync(cov + (size_t)b * M * M, sizeof(double) * M,
                                  bt->covw + (size_t)b * scv, sizeof(double) * Mp,
                                  sizeof(double) * M, M, hipMemcpyDeviceToDevice, s));
+    }
+    if (st) {
+      // the sampler on the padded covariance where it lies (factored in place), no copy-out
+      const long long Sp = ((long long)st->S + 63) / 64 * 64;
+      {
+        const int e = ensure(ctx, bt->samp, bt->samp_cap, (size_t)bt->B * 2 * Sp * Mp);
+        if (e != GPX_OK) return e;
+      }
+      if (!bt->d_sinfo) HIPX(ctx, hipMalloc(&bt->d_sinfo, sizeof(int) * bt->B));
+      SampleArgs sa{};
+      sa.active = bt->d_active;
+      sa.cov = bt->covw; sa.sCov = scv; sa.ldc = Mp;
+      sa.white = st->white; sa.sWhite = (long long)st->S * M;
+      sa.mean = mean; sa.sMean = M;
+      sa.out = st->out; sa.sOut = (long long)st->S * M;
+      sa.A = bt->covw; sa.sA = scv;
+      sa.Wp = bt->samp; sa.P = bt->samp + Sp * Mp; sa.sW = 2 * Sp * Mp;
+      sa.info = bt->d_sinfo;
+      sa.M = M; sa.S = st->S; sa.Mp = Mp; sa.Sp = (int)Sp; sa.jitter = st->jitter;
+      launch_sample_chain(sa, n_active, s);
     }
   } else {
   // A = W · Kxs with fused column sum of squares
@@ -296,6 +332,11 @@ static int predict_impl(gpx_batch* bt, int n_active, const int32_t* active, cons
     return shadow_status;
   }
   HIPX(ctx, hipMemcpyAsync(bt->h_info, bt->d_info, sizeof(int) * bt->B, hipMemcpyDeviceToHost, s));
+  std::vector<int> sinfo;
+  if (st) {
+    sinfo.assign(bt->B, 0);
+    HIPX(ctx, hipMemcpyAsync(sinfo.data(), bt->d_sinfo, sizeof(int) * bt->B, hipMemcpyDeviceToHost, s));
+  }
   HIPX(ctx, hipStreamSynchronize(s));
   if (pt.on) {
     bt->timing.factor_ms = pt.ms(0, 1);
@@ -314,11 +355,17 @@ static int predict_impl(gpx_batch* bt, int n_active, const int32_t* active, cons
     if (info[b] != 0) {
       status = GPX_NOT_PD;
       bt->fac_valid[b] = 0;
+      if (st) st->failed |= 1;
     } else if (was_refac) {
       std::memcpy(&bt->fac_theta[(size_t)b * GPX_THETA_STRIDE], theta + (size_t)b * GPX_THETA_STRIDE,
                   sizeof(double) * GPX_THETA_STRIDE);
       bt->fac_valid[b] = 1;
       bt->fac_band[b] = 0;
+    }
+    if (st && info[b] == 0 && sinfo[b] != 0) {  // (K's factor is good and stays cached)
+      info[b] = sinfo[b];
+      status = GPX_NOT_PD;
+      st->failed |= 2;
     }
   }
   if (shadow_status == GPX_NOT_PD) status = GPX_NOT_PD;
@@ -351,6 +398,32 @@ int gpx_batch_predict_full_cov(gpx_batch* bt, int n_active, const int32_t* activ
                                double* cov, int32_t* info, void* stream) {
   if (!cov) return bt ? fail(bt->ctx, GPX_BAD_ARG, "bad predict args") : GPX_BAD_ARG;
   return predict_impl(bt, n_active, active, theta, Xnew, M, 0, mean, nullptr, cov, info, stream);
+}
+
+int gpx_batch_predict_samples(gpx_batch* bt, int n_active, const int32_t* active, const double* theta,
+                              const double* Xnew, int M, int S, const double* white, double jitter,
+                              double* mean, double* out, int32_t* info, void* stream) {
+  if (!bt) return GPX_BAD_ARG;
+  gpx_ctx* ctx = bt->ctx;
+  if (!active || !theta || !Xnew || !white || !mean || !out || !info)
+    return fail(ctx, GPX_BAD_ARG, "gpx_batch_predict_samples: null pointer");
+  if (M <= 0 || S <= 0) return fail(ctx, GPX_BAD_ARG, "gpx_batch_predict_samples: M and S must be positive");
+  if (M > kSampleMaxM)
+    return fail(ctx, GPX_BAD_ARG, "gpx_batch_predict_samples: M over the limit (gpx_sample_limits)");
+  if (!(jitter >= 0.0) || !std::isfinite(jitter))
+    return fail(ctx, GPX_BAD_ARG, "gpx_batch_predict_samples: jitter must be finite and >= 0");
+  const long long rows = ((long long)M + 63) / 64 * 64 + ((long long)S + 63) / 64 * 64;
+  if (n_active <= 0 || n_active > bt->B || (long long)n_active * rows > 0x7fffffffLL)
+    return fail(ctx, GPX_BAD_ARG, "gpx_batch_predict_samples: bad active set, or too many problems x rows for one call");
+  SampleTail st{S, white, jitter, out, 0};
+  const int rc = predict_impl(bt, n_active, active, theta, Xnew, M, 0, mean, nullptr, nullptr, info, stream, false,
+                              false, &st);
+  if (rc == GPX_NOT_PD) {
+    const char* k = "K + noise*I is not positive definite for some problem";
+    const char* p = "the posterior covariance + jitter*I is not positive definite for some problem";
+    last_error_slot() = (st.failed & 1) ? ((st.failed & 2) ? std::string(k) + "; " + p : std::string(k)) : std::string(p);
+  }
+  return rc;
 }
 
 }  // extern "C"

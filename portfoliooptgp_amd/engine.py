@@ -139,6 +139,65 @@ def set_default_band_route(route: str) -> str:
     return prev
 
 
+DEFAULT_JITTER = 1e-6  # GPflow's default_jitter(), what its sample_mvn adds to the covariance's diagonal
+
+
+def check_jitter(jitter) -> float:
+    jitter = float(jitter)
+    if not (np.isfinite(jitter) and jitter >= 0.0):
+        raise ValueError(f"jitter must be finite and >= 0, got {jitter}")
+    return jitter
+
+
+def sample_limits() -> int:
+    """The largest M of one sampler call (gpx_sample_limits; needs no device)."""
+    m = ctypes.c_int()
+    if N.load_library().gpx_sample_limits(ctypes.byref(m)) != N.GPX_OK:
+        raise N.GPXError("gpx_sample_limits failed")
+    return m.value
+
+
+def sample_mvn(mean: torch.Tensor, cov: torch.Tensor, white: torch.Tensor, jitter: float = DEFAULT_JITTER):
+    """mean + chol(cov + jitter·I) · white for a batch of Gaussians on the device (gpx_sample_mvn,
+    GPflow's sample_mvn(full_cov=True) arithmetic). mean [B, M], cov [B, M, M] (its lower triangle is
+    read), white [B, S, M], fp64 device tensors on one device (or unbatched: [M], [M, M], [S, M]).
+    Returns the draws [B, S, M] ([S, M]). A problem's bits do not depend on what shares the call,
+    and sample s does not depend on S. Raises NotPositiveDefiniteError (its ``info``: the first
+    failing pivot per problem, 1-based) if some cov + jitter·I has no Cholesky factor."""
+    jitter = check_jitter(jitter)
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in (mean, cov, white)):
+        raise ValueError("sample_mvn takes device tensors (there is no CPU fallback)")
+    single = mean.ndim == 1
+    if single:
+        mean, cov, white = mean.unsqueeze(0), cov.unsqueeze(0), white.unsqueeze(0)
+    if mean.ndim != 2 or cov.ndim != 3 or white.ndim != 3:
+        raise ValueError("sample_mvn needs mean [B, M], cov [B, M, M] and white [B, S, M]")
+    B, M = mean.shape
+    S = white.shape[1]
+    if cov.shape != (B, M, M) or white.shape != (B, S, M) or M == 0 or S == 0 or B == 0:
+        raise ValueError(f"sample_mvn shapes do not agree: mean {tuple(mean.shape)}, cov {tuple(cov.shape)}, "
+                         f"white {tuple(white.shape)}")
+    device = mean.device.index
+    if cov.device != mean.device or white.device != mean.device:
+        raise ValueError("sample_mvn needs its tensors on one device")
+    ctx = N.Context.get(device)
+    mean, cov, white = (t.detach().to(torch.float64).contiguous() for t in (mean, cov, white))
+    out = torch.empty(B, S, M, dtype=torch.float64, device=mean.device)
+    info = np.zeros(B, dtype=np.int32)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    rc = ctx.lib.gpx_sample_mvn(ctx.handle, B, M, S, ctypes.c_void_p(mean.data_ptr()), ctypes.c_void_p(cov.data_ptr()),
+                                ctypes.c_void_p(white.data_ptr()), jitter, ctypes.c_void_p(out.data_ptr()),
+                                info.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), stream)
+    if rc == N.GPX_NOT_PD:
+        bad = [b for b in range(B) if info[b] != 0]
+        raise N.NotPositiveDefiniteError(
+            f"Cholesky decomposition was not successful (problems {bad}, pivots {[int(info[b]) for b in bad]}): "
+            f"{ctx.last_error()}", info)
+    if rc != N.GPX_OK:
+        raise N.GPXError(f"gpx_sample_mvn failed ({rc}): {ctx.last_error()}")
+    return out[0] if single else out
+
+
 class Engine:
     def __init__(self, Xs: Sequence, Ys: Sequence, specs: Sequence[N.GpxKernelSpec],
                  device: Optional[int] = None, band_storage: bool = False, band_route: Optional[str] = None):
@@ -492,6 +551,69 @@ class Engine:
         else:
             outs_v = [var[k, : x.shape[0]] for k, x in zip(rows, xs)]
         return outs_m, outs_v, info
+
+    def predict_samples(self, active: Sequence[int], theta: np.ndarray, Xnew: Sequence, whites: Sequence,
+                        jitter: float = DEFAULT_JITTER):
+        """Joint posterior draws of the latent f at Xnew[i] for problem active[i], one device pass
+        (gpx_batch_predict_samples: the covariance never leaves the batch's workspace). whites[i] is
+        the standard-normal input [S, M_i] (device or host), S the same for every problem. Returns
+        (means, samples, info): lists of device tensors [M_i] and [S, M_i]. A ragged call is padded
+        to the longest Xnew with zero rows; a problem's factor is a function of its own leading
+        block, so its draws are its solo call's bit for bit — and where only the padding of a padded
+        problem fails to factor, that problem is run again on its own."""
+        act = self._active(active)
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        xs = [_rows(to_device_f64(x, self.device), self.D) for x in Xnew]
+        if any(x.shape[1] != self.D for x in xs):
+            raise ValueError(f"Xnew must have {self.D} columns")
+        ws = [to_device_f64(w, self.device) for w in whites]
+        if len(xs) != len(act) or len(ws) != len(act):
+            raise ValueError("predict_samples needs one Xnew and one white per active problem")
+        S = ws[0].shape[0] if ws[0].ndim == 2 else -1
+        if S <= 0 or any(w.ndim != 2 or w.shape != (S, x.shape[0]) for w, x in zip(ws, xs)):
+            raise ValueError("each white must be [S, M_i] with one S >= 1 for the whole call")
+        M = max(x.shape[0] for x in xs)
+        if M == 0:
+            raise ValueError("predict_samples needs at least one prediction point")
+        check_jitter(jitter)
+        dev = f"cuda:{self.device}"
+        Xn = torch.zeros(self.B, M, self.D, dtype=torch.float64, device=dev)
+        Wn = torch.zeros(self.B, S, M, dtype=torch.float64, device=dev)
+        for b, x, w in zip(act, xs, ws):
+            Xn[b, : x.shape[0]] = x
+            Wn[b, :, : x.shape[0]] = w
+        mean = torch.empty(self.B, M, dtype=torch.float64, device=dev)
+        out = torch.empty(self.B, S, M, dtype=torch.float64, device=dev)
+        info = np.zeros(self.B, dtype=np.int32)
+        dp = ctypes.POINTER(ctypes.c_double)
+        ip = ctypes.POINTER(ctypes.c_int32)
+        rc = self.lib.gpx_batch_predict_samples(
+            self.handle, len(act), act.ctypes.data_as(ip), theta.ctypes.data_as(dp), ctypes.c_void_p(Xn.data_ptr()),
+            M, S, ctypes.c_void_p(Wn.data_ptr()), float(jitter), ctypes.c_void_p(mean.data_ptr()),
+            ctypes.c_void_p(out.data_ptr()), info.ctypes.data_as(ip), self._stream())
+        self._harvest_boxes()
+        if rc not in (N.GPX_OK, N.GPX_NOT_PD):
+            raise N.GPXError(f"gpx_batch_predict_samples failed ({rc}): {self.ctx.last_error()}")
+        msg = self.ctx.last_error() if rc == N.GPX_NOT_PD else ""
+        means = {int(b): mean[b, : x.shape[0]] for b, x in zip(act, xs)}
+        outs = {int(b): out[b, :, : x.shape[0]] for b, x in zip(act, xs)}
+        if rc == N.GPX_NOT_PD:
+            # a pivot inside a problem's own rows is its failure; one in the zero rows a ragged call
+            # padded it with says nothing about the problem: that one runs again alone
+            # (only when every failure of the call is the posterior covariance's: K's pivots count N rows)
+            padded = not msg.startswith("K + noise")
+            again = [k for k, (b, x) in enumerate(zip(act, xs))
+                     if padded and info[b] > x.shape[0] and x.shape[0] < M]
+            bad = [int(b) for k, b in enumerate(act) if info[b] != 0 and k not in again]
+            if bad:
+                raise N.NotPositiveDefiniteError(
+                    f"Cholesky decomposition was not successful (problems {bad}, pivots "
+                    f"{[int(info[b]) for b in bad]}): {msg}", info)
+            for k in again:
+                b = act[k]
+                m1, o1, i1 = self.predict_samples([b], theta, [xs[k]], [ws[k]], jitter)
+                means[int(b)], outs[int(b)], info[b] = m1[0], o1[0], i1[b]
+        return [means[int(b)] for b in act], [outs[int(b)] for b in act], info
 
     def _predict_train(self, act: np.ndarray, theta: np.ndarray, add_noise: bool, column: bool = False):
         """predict at each problem's own training inputs: O(N²) from the cached factor

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .engine import Engine, default_device, solo_engine
+from .engine import DEFAULT_JITTER, Engine, check_jitter, default_device, solo_engine
 from .kernels import Kernel, compile_spec, coregion_term, has_ard, has_coregion
 from .likelihoods import Gaussian, StudentT
 from .mean_functions import MeanFunction, Zero
@@ -41,6 +41,45 @@ def _refuse_coregion(kernel: Kernel, model: str) -> None:
     if has_coregion(kernel):
         raise NotImplementedError(f"{model} does not take kernels with a Coregion term: Coregion is "
                                   "implemented for models.GPR")
+
+
+def _gaussian_log_density(model, data) -> torch.Tensor:
+    """GPflow's GPModel.predict_log_density for a Gaussian likelihood: log N(Ynew | predict_y's mean,
+    predict_y's variance), summed over the output column -> [N*]. Placed like predict_y's outputs."""
+    if not isinstance(model.likelihood, Gaussian):
+        raise NotImplementedError("predict_log_density is implemented for the Gaussian likelihood (GPflow "
+                                  "integrates other likelihoods by quadrature)")
+    Xnew, Ynew = data
+    mean, var = model.predict_y(Xnew)
+    y = Ynew if isinstance(Ynew, torch.Tensor) else torch.as_tensor(np.asarray(Ynew, dtype=np.float64))
+    y = y.to(device=mean.device, dtype=torch.float64).reshape(-1, 1)
+    if y.shape != mean.shape:
+        raise ValueError(f"Ynew must have one row per row of Xnew ({mean.shape[0]}), got {tuple(y.shape)}")
+    return (-0.5 * (np.log(2.0 * np.pi) + torch.log(var) + (y - mean) ** 2 / var)).sum(dim=-1)
+
+
+def _nrows(x) -> int:
+    return int(x.shape[0]) if hasattr(x, "shape") and len(x.shape) > 0 else len(x)
+
+
+def _sample_args(Xnew, num_samples, white, jitter, full_cov: bool, full_output_cov: bool):
+    """predict_f_samples' argument checks, before anything touches a device: (S, N*, white as a
+    float64 tensor [S, N*] or None, jitter)."""
+    if full_cov and full_output_cov:
+        # GPflow 2.9 GPModel.predict_f_samples raises for this too
+        raise NotImplementedError("The combination of both `full_cov` and `full_output_cov` is not permitted.")
+    if num_samples is not None and (int(num_samples) != num_samples or num_samples <= 0):
+        raise ValueError(f"num_samples must be a positive integer or None, got {num_samples}")
+    S = 1 if num_samples is None else int(num_samples)
+    jitter = DEFAULT_JITTER if jitter is None else check_jitter(jitter)
+    nstar = _nrows(Xnew)
+    if white is not None:
+        w = white if isinstance(white, torch.Tensor) else torch.as_tensor(np.asarray(white, dtype=np.float64))
+        want = (nstar, 1) if num_samples is None else (S, nstar, 1)
+        if tuple(w.shape) != want:
+            raise ValueError(f"white must have shape {want}, got {tuple(w.shape)}")
+        white = w.detach().to(torch.float64).reshape(S, nstar)
+    return S, nstar, white, jitter
 
 
 class GPR:
@@ -286,6 +325,83 @@ class GPR:
             m, v = m.cpu(), v.cpu()
         return m, v
 
+    def predict_log_density(self, data, full_cov: bool = False, full_output_cov: bool = False):
+        """log p(Ynew | Xnew) per point, [N*]: the Gaussian log density of Ynew under predict_y."""
+        if full_cov or full_output_cov:
+            raise NotImplementedError("The predict_log_density method currently supports only the argument "
+                                      "values full_cov=False and full_output_cov=False")
+        return _gaussian_log_density(self, data)
+
+    def predict_f_samples(self, Xnew, num_samples: Optional[int] = None, full_cov: bool = True,
+                          full_output_cov: bool = False, *, white=None, generator=None, jitter=None):
+        """Draws from the posterior of the latent f at Xnew: [S, N*, 1], or [N*, 1] when
+        ``num_samples`` is None (GPflow's GPModel.predict_f_samples and its sample_mvn arithmetic).
+        With full_cov the draws are joint, mean + chol(cov + jitter·I)·white on the device (the
+        covariance never leaves it); without, mean + sqrt(var)·white per point (no jitter, no clamp).
+        ``white``: the standard-normal input, [S, N*, 1] ([N*, 1] without num_samples); absent, it is
+        drawn by torch.randn on the model's device with ``generator``. ``jitter``: None is GPflow's
+        default 1e-6. Outputs are placed like predict_f's."""
+        S, nstar, white, jitter = _sample_args(Xnew, num_samples, white, jitter, full_cov, full_output_cov)
+        return _predict_f_samples([self], [Xnew], S, full_cov, [white], generator, jitter,
+                                  squeeze=num_samples is None)[0]
+
+
+def _predict_f_samples(models, Xnews, S: int, full_cov: bool, whites, generator, jitter: float,
+                       squeeze: bool = False):
+    """predict_f_samples of models that share one engine, after the argument checks: one device pass."""
+    eng, _ = models[0].engine()
+    idx = [m.engine()[1] for m in models]
+    dev = f"cuda:{eng.device}"
+    for m, x in zip(models, Xnews):
+        if m._coreg is not None:  # (a Coregion term: Xnew's index column is checked like X's)
+            xn = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x, dtype=np.float64)
+            m._coreg.check_index(xn.reshape(xn.shape[0], -1) if xn.ndim != 2 else xn, "Xnew")
+    whites = [torch.randn(S, _nrows(x), dtype=torch.float64, device=dev, generator=generator) if w is None
+              else w.to(dev) for w, x in zip(whites, Xnews)]
+    theta = np.ones((eng.B, N.GPX_THETA_STRIDE))
+    for m, b in zip(models, idx):
+        theta[b] = m.theta_row()
+    out = [None] * len(models)
+    live = [k for k, x in enumerate(Xnews) if _nrows(x) > 0]
+    for k in set(range(len(models))) - set(live):
+        out[k] = torch.empty(S, 0, dtype=torch.float64, device=dev)
+    if live and full_cov:
+        _, smp, _ = eng.predict_samples([idx[k] for k in live], theta, [Xnews[k] for k in live],
+                                        [whites[k] for k in live], jitter)
+        for k, s in zip(live, smp):
+            out[k] = s
+    elif live:
+        ms, vs, _ = eng.predict([idx[k] for k in live], theta, [Xnews[k] for k in live], False)
+        for k, m, v in zip(live, ms, vs):
+            out[k] = m.reshape(1, -1) + torch.sqrt(v).reshape(1, -1) * whites[k]
+    res = []
+    for x, s in zip(Xnews, out):
+        s = s.unsqueeze(-1)
+        if squeeze:
+            s = s[0]
+        res.append(s.cpu() if not (isinstance(x, torch.Tensor) and x.is_cuda) else s)
+    return res
+
+
+def predict_f_samples_batch(models: Sequence[GPR], Xnews: Sequence, num_samples: int, full_cov: bool = True,
+                            whites: Optional[Sequence] = None, generator=None, jitter=None):
+    """predict_f_samples for several models in one device pass when they share an engine (fitted by
+    Scipy().minimize_batch), like predict_f_batch; otherwise one by one. Ragged N* is padded per
+    call; each model's draws equal its own predict_f_samples call bit for bit (same ``white``).
+    ``whites``: one [S, N*_i, 1] per model, or None. Returns a list of [S, N*_i, 1]."""
+    if num_samples is None:
+        raise ValueError("predict_f_samples_batch needs num_samples")
+    whites = [None] * len(models) if whites is None else list(whites)
+    if len(Xnews) != len(models) or len(whites) != len(models):
+        raise ValueError("predict_f_samples_batch needs one Xnew (and one white) per model")
+    args = [_sample_args(x, num_samples, w, jitter, full_cov, False) for x, w in zip(Xnews, whites)]
+    S, jit = args[0][0], args[0][3]
+    shared = all(m._engine is not None for m in models) and len({id(m.engine()[0]) for m in models}) == 1
+    if not shared:
+        return [_predict_f_samples([m], [x], S, full_cov, [a[2]], generator, jit)[0]
+                for m, x, a in zip(models, Xnews, args)]
+    return _predict_f_samples(list(models), list(Xnews), S, full_cov, [a[2] for a in args], generator, jit)
+
 
 def predict_f_batch(models: Sequence[GPR], Xnews: Sequence, add_noise: bool = False):
     """predict_f (or predict_y) for several models sharing one engine, in one device pass.
@@ -490,6 +606,11 @@ class SVGP:
             raise NotImplementedError("SVGP.predict_f supports full_cov=False (marginals)")
         return self._predict(Xnew, False)
 
+    def predict_log_density(self, data):
+        """log p(Ynew | Xnew) per point, [N*], under predict_y (Gaussian likelihood; with StudentT
+        GPflow integrates by quadrature: NotImplementedError)."""
+        return _gaussian_log_density(self, data)
+
     def predict_y(self, Xnew, full_cov: bool = False, full_output_cov: bool = False):
         if full_cov or full_output_cov:
             raise NotImplementedError("The predict_y method currently supports only the argument "
@@ -669,6 +790,10 @@ class SGPR:
         if full_cov or full_output_cov:
             raise NotImplementedError("SGPR.predict_f supports full_cov=False (marginals)")
         return self._predict(Xnew, False)
+
+    def predict_log_density(self, data):
+        """log p(Ynew | Xnew) per point, [N*]: the Gaussian log density of Ynew under predict_y."""
+        return _gaussian_log_density(self, data)
 
     def predict_y(self, Xnew, full_cov: bool = False, full_output_cov: bool = False):
         if full_cov or full_output_cov:
@@ -852,6 +977,11 @@ class VGP:
         if full_cov or full_output_cov:
             raise NotImplementedError("VGP.predict_f supports full_cov=False (marginals)")
         return self._predict(Xnew, False)
+
+    def predict_log_density(self, data):
+        """log p(Ynew | Xnew) per point, [N*], under predict_y (Gaussian likelihood; with StudentT
+        GPflow integrates by quadrature: NotImplementedError)."""
+        return _gaussian_log_density(self, data)
 
     def predict_y(self, Xnew, full_cov: bool = False, full_output_cov: bool = False):
         if full_cov or full_output_cov:

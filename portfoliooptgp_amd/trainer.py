@@ -89,6 +89,28 @@ def unstack_assets(values, X_aug, index_dim: int, n_assets: Optional[int] = None
     return [v[idx == p] for p in range(P)]
 
 
+def sample_asset_paths(model, X_aug_new, index_dim: int, num_samples: int, **kw):
+    """Joint posterior draws per asset and day from a multi-asset (Coregion) model: ``X_aug_new`` is
+    a stack_assets-style Xnew, every asset with the same number H of rows; returns ``[S, H, P]``,
+    column p holding asset p's rows in their stacked order (as unstack_assets groups them). The draws
+    are ``model.predict_f_samples(X_aug_new, num_samples, **kw)`` regrouped — joint across assets
+    and days with the default full_cov=True."""
+    idx = np.asarray(_np(X_aug_new), dtype=np.float64)
+    if idx.ndim != 2 or not (0 <= index_dim < idx.shape[1]):
+        raise ValueError(f"X_aug_new must be [rows, D+1] with the asset index in column {index_dim}")
+    idx = idx[:, index_dim].astype(np.int64)
+    if idx.size == 0:
+        raise ValueError("sample_asset_paths needs at least one row")
+    counts = np.bincount(idx)
+    if np.any(counts != counts[0]):
+        raise ValueError(f"every asset must have the same number of rows, got {counts.tolist()}")
+    samples = model.predict_f_samples(X_aug_new, num_samples, **kw)   # [S, rows, 1]
+    S = samples.shape[0]
+    # asset p's rows in stacked order: a stable sort by the index column
+    order = torch.as_tensor(np.argsort(idx, kind="stable"), device=samples.device)
+    return samples[:, order, 0].reshape(S, len(counts), int(counts[0])).transpose(1, 2).contiguous()
+
+
 class ModelTrainer:
     def __init__(self, kernel_combinations: Sequence, device: Optional[int] = None):
         self.kernel_combinations = list(kernel_combinations)
